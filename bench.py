@@ -401,6 +401,11 @@ def main():
     ap.add_argument("--run", type=int, default=0, metavar="B",
                     help="submit the steps B at a time through oalgpu_mix_update_run (one library call per B updates "
                          "instead of two per update); B must divide --steps and --warmup; 0 = one update per call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed block, write what its last step computed -- the output a caller reads back -- as "
+                         "DIR/<name>.npy (float32; rank 0): dry.npy = oalgpu_read_dry (the dry lines, then the real output lines), "
+                         "and for config 2 pcm_s16.npy = oalgpu_read_output (interleaved 8-channel s16 PCM, as float32).  The "
+                         "inputs are seeded: the same arguments give the same inputs on every run")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) would measure ONE GPU and call it N: it starts itself again as
@@ -615,6 +620,14 @@ def main():
         step(k)
     fence()
     elapsed, own_elapsed = timed_block(args.warmup)
+    if args.dump_outputs and rank == 0:
+        # read back behind the timed block's closing fence, before any later pass mixes another update
+        dump = {"dry": sc.dry()}
+        if args.config == 2:
+            dump["pcm_s16"] = sc.read_output(UPDATE_SAMPLES, 8).astype(np.float32)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, np.float32))
     rank_ms = [own_elapsed / args.steps * 1e3]
     if dist is not None:
         tt = torch.zeros(world, dtype=torch.float64, device=tdev)

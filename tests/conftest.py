@@ -24,9 +24,7 @@ def synth_mhr(tmp_path_factory):
 @pytest.fixture(scope="session")
 def mhr_paths(synth_mhr):
     """All data sets to test with: the synthetic one, plus the reference's own Default HRTF
-    when /root/reference is mounted (dev container only; it never travels to the GPU box)."""
-    paths = [synth_mhr]
-    real = "/root/reference/hrtf/Default HRTF.mhr"
-    if os.path.exists(real):
-        paths.append(real)
-    return paths
+    (tests/golden/default_hrtf.mhr, a committed byte-for-byte copy)."""
+    real = os.path.join(ROOT, "tests", "golden", "default_hrtf.mhr")
+    assert os.path.exists(real), "tests/golden/default_hrtf.mhr is a committed fixture"
+    return [synth_mhr, real]
