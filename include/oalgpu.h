@@ -176,7 +176,10 @@ typedef struct oalgpu_context_desc {
     int32_t  hrtf;                /* RenderMode::Hrtf: voices use the dual-ear FIR */
     uint32_t max_voices;
     uint32_t max_buffers;
-    uint32_t voices_per_group;    /* 0 = choose automatically (tuning knob) */
+    uint32_t voices_per_group;    /* 0 = choose automatically (tuning knob).  FAST HRTF contexts whose voices get a
+                                   * wavefront each (csrc/voice_wave16.hip): the narrowest of 4, 8 and 16 voices per workgroup whose
+                                   * grid fits the partial buses -- sized for the larger of this value's grid and the automatic one --
+                                   * or, if none does, two voices per wavefront at this many voices per workgroup */
     uint32_t flags;               /* OALGPU_CTX_* below; 0 = the product configuration */
 } oalgpu_context_desc;
 /* oalgpu_context_desc::flags -- kernel variants are chosen here, never from the environment */

@@ -130,6 +130,15 @@ int FlushInits(oalgpu_context *c)
 
 static void SetRowsGroups(oalgpu_context *c);      // (voice_rows.hip's grid; defined beside RebalanceWaveGroups)
 
+// the device's compute units (256 on an MI355X, the figure assumed when the query fails)
+uint32_t DeviceComputeUnits(int device)
+{
+    hipDeviceProp_t prop{};
+    if(hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) return uint32_t(prop.multiProcessorCount);
+    (void)hipGetLastError();
+    return 256u;
+}
+
 int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
 {
     if(!desc || !out) return Fail(OALGPU_ERR_INVALID, "null argument");
@@ -232,6 +241,12 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     HIP_TRY(c->queueDone.alloc(nv)); HIP_TRY(c->queueDone.zero()); L.queueDone = c->queueDone.p;
     L.numLineGroups = L.numGroups;
     c->groupsAllocated = L.numGroups;
+    if(c->useWave && L.hrtf && L.firMfma && !(desc->flags & OALGPU_CTX_WAVE_PAIRS))
+    {   // the voice-per-wavefront form InstallHrtfData may choose (voice_wave16.hip) has a grid of voices / 4, 8 or 16 workgroups: above
+        // 8192 voices, or with voices_per_group, more than the two-voices-per-wavefront grid above -- the partial buses fit the larger
+        const uint32_t w = Wave16WavesFor(desc->max_voices, DeviceComputeUnits(desc->device));
+        c->groupsAllocated = std::max<uint32_t>(c->groupsAllocated, (desc->max_voices + w - 1u) / w);
+    }
     L.streams = nullptr; L.lineGains = nullptr; L.lineStride = 0; L.streamsPerVoice = 0;
     L.nfc = nullptr; L.nfcOrders = 0;
     L.hrirs = nullptr;
@@ -260,12 +275,13 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
         L.streamsPerVoice = 2u + L.numSends;
     }
     if(c->useWave && (!L.hrtf || L.numSends) && !L.accLines && !L.sliceLines && !L.rows8) { if(int rc = AllocStreamRows(c.get())) return rc; }
-    HIP_TRY(c->partLines.alloc(size_t{L.numLineGroups} * L.mixLines * kLine)); L.partLines = c->partLines.p;
+    const size_t groups = c->groupsAllocated;
+    HIP_TRY(c->partLines.alloc(groups * L.mixLines * kLine)); L.partLines = c->partLines.p;
     // the two-stream pipeline of oalgpu_mix_update alternates between two sets of partial buses
-    HIP_TRY(c->partLines2.alloc(c->useWave && (L.streams || L.accLines || L.sliceLines || L.rows8) ? size_t{L.numLineGroups} * L.mixLines * kLine : 0));
+    HIP_TRY(c->partLines2.alloc(c->useWave && (L.streams || L.accLines || L.sliceLines || L.rows8) ? groups * L.mixLines * kLine : 0));
     c->partLinesBuf[0] = c->partLines.p; c->partLinesBuf[1] = c->partLines2.p;
-    HIP_TRY(c->partHrtf.alloc(L.hrtf ? size_t{L.numGroups} * (kLine + kHrirLen) * 2 : 0)); L.partHrtf = c->partHrtf.p;
-    HIP_TRY(c->partHrtf2.alloc(c->useWave && L.hrtf ? size_t{L.numGroups} * (kLine + kHrirLen) * 2 : 0));
+    HIP_TRY(c->partHrtf.alloc(L.hrtf ? groups * (kLine + kHrirLen) * 2 : 0)); L.partHrtf = c->partHrtf.p;
+    HIP_TRY(c->partHrtf2.alloc(c->useWave && L.hrtf ? groups * (kLine + kHrirLen) * 2 : 0));
     c->partHrtfBuf[0] = c->partHrtf.p; c->partHrtfBuf[1] = c->partHrtf2.p;
     HIP_TRY(c->bus.alloc(BusFloats(L))); HIP_TRY(c->bus.zero()); L.bus = c->bus.p;
     if(desc->flags & OALGPU_CTX_PROFILE)
@@ -998,10 +1014,7 @@ static void SetRowsGroups(oalgpu_context *c)
     DeviceLayout &L = c->L;
     uint32_t reverbs = 0;
     for(oalgpu_reverb *r : c->slotReverb) reverbs += r ? 1u : 0u;
-    uint32_t cus = 256u;
-    hipDeviceProp_t prop{};
-    if(hipGetDeviceProperties(&prop, c->desc.device) == hipSuccess && prop.multiProcessorCount > 0) cus = uint32_t(prop.multiProcessorCount);
-    else (void)hipGetLastError();
+    const uint32_t cus = DeviceComputeUnits(c->desc.device);
     const uint32_t waves = RowsWavesPerGroup();
     uint32_t groups = std::min<uint32_t>(cus > reverbs ? cus - reverbs : 1u, (L.numVoices + waves - 1u) / waves);
     if(c->desc.voices_per_group) groups = (L.numVoices + c->desc.voices_per_group - 1u) / c->desc.voices_per_group;

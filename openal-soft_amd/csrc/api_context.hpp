@@ -351,6 +351,7 @@ void RetireCallbackVoice(oalgpu_context *c, uint32_t voice);
 void NoteCallbackSteps(oalgpu_context *c, const uint32_t *voices, const oalgpu_voice_params *params, size_t count);
 int FlushInits(oalgpu_context *c);
 int AllocStreamRows(oalgpu_context *c);
+uint32_t DeviceComputeUnits(int device);
 int JoinPost(oalgpu_context *c);
 bool HostStoresReachDevice(oalgpu_context *c);                     // api_voices.hip
 int AllocBufferHandle(oalgpu_context *c, uint32_t *out);           // api_voices.hip

@@ -1,12 +1,43 @@
 // HRTF data sets: .mhr / store hand-over, getCoeffs on the device, the direct-HRTF decoder, host-side helpers.
 #include "api_context.hpp"
 
+// wavefronts per workgroup of the voice-per-wavefront form (voice_wave16.hip) for a context whose layout is T, 0 = the
+// two-voices-per-wavefront kernel.  By default the device decides (Wave16WavesFor); with voices_per_group the narrowest of 4 / 8 / 16 whose
+// grid fits the partial buses (oalgpu_context_create sized them for the larger of the two grids), and none: the pairs kernel.
+static uint32_t ChooseWave16(const oalgpu_context *c, const DeviceLayout &T)
+{
+    // (with sends: the voice-per-wavefront kernel leaves the sends' signals as stream rows and a small kernel behind it mixes them --
+    // the HRTF path keeps its four wavefronts per SIMD; OALGPU_CTX_WAVE_PAIRS keeps the wet lines in the registers of the
+    // two-voices-per-wavefront kernel, OALGPU_CTX_STREAM_ROWS its stream rows)
+    const bool want16 = !(c->desc.flags & OALGPU_CTX_WAVE_PAIRS) && Wave16Applies(T)
+        && (T.numSends == 0 || !(c->desc.flags & (OALGPU_CTX_STREAM_ROWS | OALGPU_CTX_PROFILE | OALGPU_CTX_SLICE_LINES)));
+    if(!want16) return 0u;
+    if(!c->desc.voices_per_group) return Wave16WavesFor(T.numVoices, DeviceComputeUnits(c->desc.device));
+    for(uint32_t w : {4u, 8u, 16u})
+        if((T.numVoices + w - 1u) / w <= c->groupsAllocated) return w;
+    return 0u;
+}
+
 // the parsed (or handed-over) store becomes the context's: host copy, HBM copy, voice filter arrays
 static int InstallHrtfData(oalgpu_context *c, HrtfData &&parsed)
 {
     // a data set at another rate than the device's is brought to the device's rate as GetLoadedHrtf does
     // (core/hrtf.cpp:539-606: every HRIR through the polyphase resampler, delays and IrSize rescaled)
     if(parsed.sampleRate != c->desc.sample_rate) ResampleHrtfData(parsed, c->desc.sample_rate);
+    // the voice kernel's form and grid for this data set, decided before anything of the context changes: a grid the partial buses
+    // do not hold leaves the context as it was
+    DeviceLayout T = c->L;
+    T.irSize = parsed.irSize;
+    T.irStride = (parsed.irSize + 15u) & ~15u;
+    // (a set with more than 64 taps: the send rows of such an HRTF context go through stream rows)
+    const bool toStreamRows = T.accLines && WaveKernelAccLines(T) == 0;
+    if(toStreamRows) T.accLines = 0;
+    if(c->useWave)
+    {
+        T.wave16 = ChooseWave16(c, T);
+        if(std::max<uint32_t>(1u, WaveKernelGroups(T)) > c->groupsAllocated)
+            return Fail(OALGPU_ERR_INVALID, "internal: the voice kernel's grid outgrew the partial buses");
+    }
     if(int rc = oalgpu_sync(c)) return rc;           // a second load replaces buffers the streams may still read
     c->hrtfHost = std::move(parsed);
     const HrtfData &h = c->hrtfHost;
@@ -27,7 +58,7 @@ static int InstallHrtfData(oalgpu_context *c, HrtfData &&parsed)
     DeviceLayout &L = c->L;
     L.hrirs = c->hCoeffs.p;
     L.irSize = h.irSize;
-    L.irStride = (h.irSize + 15u) & ~15u;
+    L.irStride = T.irStride;
     if(L.hrtf)
     {
         const size_t n = size_t{L.numVoices} * L.irStride * 2;
@@ -35,35 +66,21 @@ static int InstallHrtfData(oalgpu_context *c, HrtfData &&parsed)
         HIP_TRY(c->hrtfTgt.alloc(n)); HIP_TRY(c->hrtfTgt.zero()); L.hrtfTgt = c->hrtfTgt.p;
         if(!c->directSet) c->dIrSize = h.irSize;
     }
-    // (a set with more than 64 taps: the send rows of such an HRTF context go through stream rows)
-    if(L.accLines && WaveKernelAccLines(L) == 0)
+    if(toStreamRows)
     {
         L.accLines = 0;
         if(int rc = AllocStreamRows(c)) return rc;
     }
-    // one voice per wavefront, sixteen per workgroup (voice_wave16.hip): its grid is voices / 16 workgroups -- never more partial
-    // buses than the context's buffers were sized for (the wavefront-per-voice kernel's grid has at least twice as many)
+    // one voice per wavefront, 4 / 8 / 16 per workgroup (voice_wave16.hip): its grid is voices / that many workgroups
     if(c->useWave)
     {
-        // (with sends: the voice-per-wavefront kernel leaves the sends' signals as stream rows and a small kernel behind it mixes them --
-        // the HRTF path keeps its four wavefronts per SIMD; OALGPU_CTX_WAVE_PAIRS keeps the wet lines in the registers of the
-        // two-voices-per-wavefront kernel, OALGPU_CTX_STREAM_ROWS its stream rows)
-        const bool want16 = !(c->desc.flags & OALGPU_CTX_WAVE_PAIRS) && Wave16Applies(L)
-            && (L.numSends == 0 || !(c->desc.flags & (OALGPU_CTX_STREAM_ROWS | OALGPU_CTX_PROFILE | OALGPU_CTX_SLICE_LINES)));
-        uint32_t cus = 256u;
-        {
-            hipDeviceProp_t prop{};
-            if(hipGetDeviceProperties(&prop, c->desc.device) == hipSuccess && prop.multiProcessorCount > 0) cus = uint32_t(prop.multiProcessorCount);
-            else (void)hipGetLastError();
-        }
-        L.wave16 = want16 ? Wave16WavesFor(L.numVoices, cus) : 0u;
+        L.wave16 = T.wave16;
         if(L.wave16 && L.numSends)
         {
             L.accLines = 0;
             if(!L.streams) { if(int rc = AllocStreamRows(c)) return rc; }
         }
         const uint32_t groups = std::max<uint32_t>(1u, WaveKernelGroups(L));
-        if(groups > c->groupsAllocated) return Fail(OALGPU_ERR_INVALID, "internal: the voice kernel's grid outgrew the partial buses");
         L.numGroups = groups; L.numLineGroups = groups;
         if(L.wave16 && (L.wave16 != 16u || L.numSends)) c->res.enabled = false;     // (the resident launch: the 16-wavefront form, or OALGPU_CTX_WAVE_PAIRS' kernel)
     }

@@ -16,12 +16,17 @@ DELAYS = {1: 1, 2: 37, 3: 700, 5: 1023, 6: 1024, 7: 1500, 9: 2500, 10: 64, 12: 5
 TODO = (1024, 700, 1024, 1024, 300)
 
 
-def run(lib, mhr, hrtf, sends, nvoices=14, stop_unstarted=(7,)):
+def run(lib, mhr, hrtf, sends, nvoices=14, stop_unstarted=(7,), split=False, on_scene=None):
+    """buses and integer voice state after every update of TODO.  split: every update's buses as a dict of float64 arrays
+    ("dry" -- dry and real lines --, "accum", "wet0", "wet1") instead of one vector; on_scene: called with the scene before
+    the first update"""
     if hrtf:
         lib.hrtf_load(mhr)
     kw = dict(max_voices=nvoices) if hasattr(lib, "device") else {}
     sc = lib.make_scene(num_dry=4 if hrtf else 5, num_real=2 if hrtf else 0, num_sends=sends, num_slots=2 if sends else 0,
                         wet_channels=4, hrtf=hrtf, **kw)
+    if on_scene is not None:
+        on_scene(sc)
     rng = np.random.default_rng(21)
     if hrtf:
         cc = np.zeros((4, 128, 2), np.float32)
@@ -48,12 +53,15 @@ def run(lib, mhr, hrtf, sends, nvoices=14, stop_unstarted=(7,)):
             for v in stop_unstarted:                        # still waiting for its start: becomes Stopped without a sound
                 sc.set_state(v, ol.VOICE_STOPPING)
         sc.mix(n, post_process=hrtf)
-        parts = [sc.dry()[:, :n].ravel()]
+        parts = {"dry": sc.dry()[:, :n].ravel()}
         if hrtf:
-            parts.append(sc.hrtf_accum().ravel())
+            parts["accum"] = sc.hrtf_accum().ravel()
         for s in range(2 if sends else 0):
-            parts.append(sc.wet(s)[:, :n].ravel())
-        out.append(np.concatenate(parts).astype(np.float64))
+            parts[f"wet{s}"] = sc.wet(s)[:, :n].ravel()
+        if split:
+            out.append({k: a.astype(np.float64) for k, a in parts.items()})
+        else:
+            out.append(np.concatenate(list(parts.values())).astype(np.float64))
         st = [sc.voice_state(v) for v in range(nvoices)]
         ints.append([(s.play_state, s.position, s.position_frac, s.has_buffer) for s in st])
     sc.close()

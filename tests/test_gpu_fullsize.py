@@ -82,9 +82,11 @@ def test_full_scene_equals_sum_of_shards(env, config):
 
 @pytest.mark.parametrize("config", [3, 2])
 def test_three_and_four_voices_per_wavefront(env, config):
-    """Above 4096 voices a wavefront of the voice kernel takes three or four voices (and the second
-    half of the grid takes them in reverse order, switching its issue priority half-way): 6000 and
-    8192 voices against the sum of shards that run at one or two voices per wavefront."""
+    """6000 and 8192 voices against the sum of shards of 2048 and 4096 voices.  Config 2 (dry lines): above 4096 voices a
+    wavefront of the voice kernel takes three or four voices (and the second half of the grid takes them in reverse order),
+    the shards one or two.  Config 3 (HRTF): every voice has a wavefront of its own, 16 voices per workgroup
+    (VoiceWave16Kernel<16>: 375 and 512 workgroups); the shards of 6000 (2048, 2048, 1904 voices) fit the machine at 8
+    voices per workgroup (VoiceWave16Kernel<8>), the 4096-voice shards of 8192 run the 16-wavefront form."""
     for total, cut in ((6000, 2048), (8192, 4096)):
         full = run_gpu(env, config, total, 0, updates=3)
         parts = [run_gpu(env, config, min(cut, total - lo), lo, updates=3) for lo in range(0, total, cut)]

@@ -22,9 +22,10 @@ def multi_voice_tolerance(num_voices, terms_per_voice, scale):
     return max(2e-5, 2.5 * reference_noise_bound(num_voices, terms_per_voice)) * scale + 1e-7
 
 
-def test_serial_fp32_accumulation_noise_matches_the_model():
-    rng = np.random.default_rng(7)
-    voices, taps, frames = 4096, 64, 96
+def _serial_noise(voices, taps, frames, seed):
+    """|serial fp32 sum - exact sum| of `frames` output frames of the bench scene's statistics, relative to the largest
+    exact frame"""
+    rng = np.random.default_rng(seed)
     # per-voice gain 10^(U(-60,-20)/20) (synth.SceneScript), source samples U(-1,1), taps decaying noise
     gains = 10.0 ** (rng.uniform(-60.0, -20.0, voices) / 20.0)
     worst = 0.0
@@ -37,7 +38,12 @@ def test_serial_fp32_accumulation_noise_matches_the_model():
         exact = np.sum(terms.astype(np.float64))
         rel.append(abs(float(serial) - exact))
         worst = max(worst, abs(exact))
-    rel = np.array(rel) / worst
+    return np.array(rel) / worst
+
+
+def test_serial_fp32_accumulation_noise_matches_the_model():
+    voices, taps = 4096, 64
+    rel = _serial_noise(voices, taps, 96, 7)
     sigma_bound = reference_noise_bound(voices, taps)
     # the measured noise is a real fraction of the bound (the running sum is below its maximum most of the
     # time, so it stays under it), i.e. the bound is the right order of magnitude -- not a loose excuse
@@ -47,3 +53,14 @@ def test_serial_fp32_accumulation_noise_matches_the_model():
     assert multi_voice_tolerance(64, 64, 1.0) == 2e-5 * 1.0 + 1e-7
     assert multi_voice_tolerance(4096, 1, 1.0) == 2e-5 * 1.0 + 1e-7          # dry-line mixes: one term per voice
     assert 4.0e-5 < multi_voice_tolerance(4096, 64, 1.0) < 5.0e-5
+
+
+def test_the_model_covers_the_reference_noise_at_10240_voices():
+    """the goal's 10 240 voices x 64 taps (tests/test_gpu_wave16_grid.py, the 10 240-voice cases of
+    tests/test_gpu_error_bound.py): the bound grows to ~7e-5 of max|ref| and the reference's own noise stays under it"""
+    voices, taps = 10240, 64
+    rel = _serial_noise(voices, taps, 64, 11)
+    sigma_bound = reference_noise_bound(voices, taps)
+    assert 0.02 * sigma_bound < rel.std() < sigma_bound, (rel.std(), sigma_bound)
+    assert rel.max() < 2.5 * sigma_bound
+    assert 6.5e-5 < multi_voice_tolerance(voices, taps, 1.0) < 7.5e-5
