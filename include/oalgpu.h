@@ -524,6 +524,39 @@ int oalgpu_set_output(oalgpu_context *ctx, int sample_type, float dither_depth, 
  * or the dry lines of a context without any), then ONE device-to-host copy of the interleaved PCM:
  * samples_to_do frames of frame_step samples (channels past the output lines are silent).  Bit-exact. */
 int oalgpu_read_output(oalgpu_context *ctx, void *out, uint32_t samples_to_do, uint32_t frame_step);
+/* ---- the output limiter: Compressor (core/mastering.cpp), run as DeviceBase::Limiter (alc/alu.cpp:2446) ----
+ * The fields mirror Compressor::Params field for field (48 bytes, the same layout).  auto_flags holds
+ * the Compressor::Flags bits in the reference's order; DECLIP is ignored without POST_GAIN.  Times are in
+ * seconds, gains and threshold in dB, ratio x:1 (INFINITY = a true limiter).  num_channels: the lines the
+ * limiter links -- the context's output lines (its real output lines, or its dry lines where it has
+ * none); 0 means exactly those. */
+enum {
+    OALGPU_LIMITER_AUTO_KNEE = 1u << 0, OALGPU_LIMITER_AUTO_ATTACK = 1u << 1, OALGPU_LIMITER_AUTO_RELEASE = 1u << 2,
+    OALGPU_LIMITER_AUTO_POST_GAIN = 1u << 3, OALGPU_LIMITER_AUTO_DECLIP = 1u << 4
+};
+typedef struct oalgpu_limiter_params {
+    uint32_t num_channels;
+    float sample_rate;
+    uint32_t auto_flags;
+    float look_ahead_time, hold_time, pre_gain_db, post_gain_db, threshold_db, ratio, knee_db, attack_time, release_time;
+} oalgpu_limiter_params;
+/* Host only.  CreateDeviceLimiter (alc/alc.cpp:1079-1090) with the threshold UpdateDeviceParams gives it
+ * (alc.cpp:1750-1768): just under full scale for 8- and 16-bit output, less 1/dither_depth with dither.
+ * sample_type: enum oalgpu_output_type.  Fills *out (num_channels = 0) and returns 1 where the reference
+ * enables the limiter by default for that format (every integer type), 0 where it does not (float),
+ * OALGPU_ERR_INVALID on bad arguments. */
+int oalgpu_limiter_device_params(uint32_t sample_rate, int sample_type, float dither_depth, oalgpu_limiter_params *out);
+/* Host only.  Compressor::getLookAhead: the limiter's delay in samples (what the reference adds to
+ * FixedLatency); 0 for NULL or invalid parameters. */
+uint32_t oalgpu_limiter_look_ahead(const oalgpu_limiter_params *params);
+/* Installs a limiter with fresh state (non-NULL params) or removes it (NULL); off by default.  It runs as
+ * the last step of every update that post-processes, on the stream that ran the post-process, over the
+ * output lines: oalgpu_read_dry, oalgpu_read_output (dither and Write<T> behind it, as in the reference),
+ * oalgpu_read_output_async / oalgpu_output_wait all see limited lines.  With a limiter set, an HRTF
+ * context's output ring is filled by a copy behind the limiter instead of by the post-process kernel.
+ * Waits for the context's work in flight.  Parity with the reference is bounded, not bit-exact: the
+ * kernel's logf / expf are the correctly rounded results, which glibc's are not everywhere. */
+int oalgpu_set_output_limiter(oalgpu_context *ctx, const oalgpu_limiter_params *params);
 
 /* Device address of the bus block [dry+real lines | wet buses | hrtf accum], its length in
  * floats, and the stream it is produced on, for zero-copy consumers: the context's main stream for

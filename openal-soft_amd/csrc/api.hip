@@ -700,7 +700,13 @@ static int ResidentSubmit(oalgpu_context *c, uint32_t samples_to_do)
     HIP_TRY(hipGetLastError());
     ++R.setUses[set];
     c->lastPostEvent = c->evPostDone;
-    if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, c->evPostDone, true)) return rc;
+    if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, c->limOn ? nullptr : c->evPostDone, true)) return rc;
+    if(c->limOn)
+    {   // the limiter behind the update's post-process; the next update's reduction (reduce stream) rewrites the lines it limits
+        if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc;
+        HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));
+        R.copyPending = c->evPostDone;
+    }
     c->postPending = true;
     ++R.next;
     ++c->updatesSubmitted;
@@ -754,6 +760,7 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
                 c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, D.numDry, c->decOut, samples_to_do);
             HIP_TRY(hipGetLastError());
         }
+        if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
         if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
         return OALGPU_OK;
     }
@@ -771,6 +778,7 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
         LaunchPostDirectHrtfFast(c->stream, left, right, L.bus, L.numDry, L.bus + BusAccumOffset(L), spCur,
             c->dHfScale.p, c->dCoeffs.p, c->dIrSize, samples_to_do, c->dTemp.p);
     HIP_TRY(hipGetLastError());
+    if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
     if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
     return OALGPU_OK;
 }
@@ -905,10 +913,11 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
     {
         // (the update's last launch on this stream, unless timing asks for an event of its own behind it: evPostDone rides on it)
         // (with the reduction in the same launch the event is the one the voice kernel of two updates on waits for as well)
-        hipEvent_t ev = c->reduceHeld ? c->evReduceDone[c->heldParity] : (c->timing ? nullptr : c->evPostDone);
-        c->lastPostEvent = ev ? ev : c->evPostDone;
+        // (a limiter is the update's last launch instead: evPostDone is recorded behind it)
+        hipEvent_t ev = c->reduceHeld ? c->evReduceDone[c->heldParity] : ((c->timing || c->limOn) ? nullptr : c->evPostDone);
+        c->lastPostEvent = (ev && !c->limOn) ? ev : c->evPostDone;
         if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, ev)) return rc;
-        postDoneBound = ev != nullptr;
+        postDoneBound = ev != nullptr && !c->limOn;
     }
     else c->lastPostEvent = c->evPostDone;
     if(post_process && !L.hrtf && c->decOn)
@@ -917,6 +926,7 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
             c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, L.numDry, c->decOut, samples_to_do);
         HIP_TRY(hipGetLastError());
     }
+    if(post_process) { if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc; }
     if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->postStream)); c->timed = true; }
     if(!postDoneBound) HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));
     c->postPending = true;

@@ -198,6 +198,10 @@ struct oalgpu_context {
     int outType{6};                        // DevFmtType order: 0 i8, 1 u8, 2 i16, 3 u16, 4 i32, 5 u32, 6 f32
     float ditherDepth{0.0f};
     uint32_t ditherSeed{22222};
+    // the output limiter (oalgpu_set_output_limiter; RunLimiter behind every post-process): its constants and device state
+    bool limOn{false};
+    LimiterConsts lim{};
+    DevBuf<float> limState;
     DevBuf<unsigned char> pcm;
     // HRTF store
     DevBuf<float> hFieldDist, hCoeffs;
@@ -353,6 +357,7 @@ int FlushInits(oalgpu_context *c);
 int AllocStreamRows(oalgpu_context *c);
 uint32_t DeviceComputeUnits(int device);
 int JoinPost(oalgpu_context *c);
+int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip
 bool HostStoresReachDevice(oalgpu_context *c);                     // api_voices.hip
 int AllocBufferHandle(oalgpu_context *c, uint32_t *out);           // api_voices.hip
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip

@@ -6,6 +6,13 @@ static size_t OutputLineFloats(const oalgpu_context *c)
     return size_t{c->L.numReal ? c->L.numReal : c->L.numDry} * kLine;
 }
 
+// The post-process kernel stores the output ring's slots itself where it writes the context's last word on the lines: an HRTF
+// context's fused FAST post-process with its two output lines, and no limiter behind it (with one, the slots take the copy).
+static bool RingEligible(const oalgpu_context *c)
+{
+    return c->L.hrtf && c->L.numReal == 2 && c->useWave && OutputLineFloats(c) == size_t{2} * kLine && !c->limOn;
+}
+
 int oalgpu_read_output_async(oalgpu_context *c, uint32_t *ticket)
 {
     if(!c || !ticket) return Fail(OALGPU_ERR_INVALID, "null argument");
@@ -29,7 +36,7 @@ int oalgpu_read_output_async(oalgpu_context *c, uint32_t *ticket)
         }
         // from the next update on the post-process kernel fills the slots itself (the fused FAST post-process of an HRTF
         // context with its two output lines; everything else keeps the copy below)
-        c->outRing = c->L.hrtf && c->L.numReal == 2 && c->useWave && floats == size_t{2} * kLine;
+        c->outRing = RingEligible(c);
     }
     const uint32_t slot = c->outNext % oalgpu_context::kIoSlots;
     if(c->outRingWritten)
@@ -209,6 +216,65 @@ int oalgpu_set_output(oalgpu_context *c, int sample_type, float dither_depth, ui
     if(!c || sample_type < OALGPU_OUT_I8 || sample_type > OALGPU_OUT_F32 || dither_depth < 0.0f)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output: bad arguments");
     c->outType = sample_type; c->ditherDepth = dither_depth; c->ditherSeed = dither_seed;
+    return OALGPU_OK;
+}
+
+/* The device's output limiter: Compressor::Create's constants (host/limiter_params.cpp), a fresh state, and from the next update
+ * on Compressor::process behind every post-process (RunLimiter) */
+int oalgpu_limiter_device_params(uint32_t sample_rate, int sample_type, float dither_depth, oalgpu_limiter_params *out)
+{
+    if(!out || sample_rate == 0 || sample_type < OALGPU_OUT_I8 || sample_type > OALGPU_OUT_F32 || !(dither_depth >= 0.0f))
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_limiter_device_params: bad arguments");
+    return LimiterDeviceParams(sample_rate, sample_type, dither_depth, out) ? 1 : 0;
+}
+
+uint32_t oalgpu_limiter_look_ahead(const oalgpu_limiter_params *params)
+{
+    LimiterConsts k{};
+    if(!params || !LimiterDerive(*params, &k)) return 0u;
+    return k.lookAhead;
+}
+
+int oalgpu_set_output_limiter(oalgpu_context *c, const oalgpu_limiter_params *params)
+{
+    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
+    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
+    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
+    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output_limiter: null context");
+    const uint32_t nlines = c->L.numReal ? c->L.numReal : c->L.numDry;
+    LimiterConsts k{};
+    if(params)
+    {
+        if(params->num_channels != 0 && params->num_channels != nlines)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output_limiter: num_channels is not the context's number of output lines");
+        if(!LimiterDerive(*params, &k))
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output_limiter: bad parameters");
+        k.numChans = nlines;
+    }
+    // the kernels of the updates in flight are through with the old state before it goes
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->limOn = false;
+    if(params)
+    {
+        std::vector<float> init(LimiterStateFloats(nlines), 0.0f);
+        std::fill(init.begin() + kLimiterHoldHistory, init.begin() + kLimiterHoldHistory + kLine, -INFINITY);
+        HIP_TRY(c->limState.alloc(init.size()));
+        HIP_TRY(c->limState.upload(init.data(), init.size()));
+        c->lim = k;
+        c->limOn = true;
+    }
+    if(c->outFloats) c->outRing = RingEligible(c);
+    return OALGPU_OK;
+}
+
+// Compressor::process behind the update's post-process, on the stream that ran it (alc/alu.cpp:2446): RealOut is the real
+// output lines, or the dry lines themselves where the context has none
+int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(!c->limOn) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    LaunchLimiter(s, L.numReal ? L.bus + size_t{L.numDry} * kLine : L.bus, samplesToDo, c->lim, c->limState.p);
+    HIP_TRY(hipGetLastError());
     return OALGPU_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "dev_mix.hpp"
 #include "dev_resample.hpp"
 #include "dev_voice.hpp"
+#include "../host/limiter_params.hpp"
 
 namespace oalgpu {
 
@@ -326,6 +327,11 @@ void LaunchBFormatDecode(hipStream_t s, bool exact, float *out, const float *lin
 void LaunchDither(hipStream_t s, float *lines, uint32_t nlines, uint32_t n, float quantScale, uint32_t seed);
 uint32_t DitherAdvanceSeed(uint32_t seed, uint32_t draws);
 void LaunchWriteSamples(hipStream_t s, int sampleType, const float *lines, uint32_t nlines, uint32_t n, uint32_t frameStep, void *out);
+// ---- launcher (limiter_kernels.hip): Compressor::process over k.numChans lines of 1024 (one workgroup); state: LimiterStateFloats
+// floats, zero but for the hold's history (-inf) when fresh ----
+void LaunchLimiter(hipStream_t s, float *lines, uint32_t n, const LimiterConsts &k, float *state);
+size_t LimiterStateFloats(uint32_t nch);
+constexpr size_t kLimiterHoldHistory = 16u + 1024u;      // where the hold's history starts in the state
 // ---- launcher (effects_kernels.hip): equalizer / modulator / echo / dedicated, one workgroup per instance ----
 constexpr uint32_t kFxMaxIn = 16;
 struct FxState {                       // device-resident per instance

@@ -189,6 +189,18 @@ def _load(path=LIB_PATH):
 lib = _load()
 
 
+class LimiterParams(C.Structure):
+    """oalgpu_limiter_params: Compressor::Params (core/mastering.h), field for field."""
+    _fields_ = [("num_channels", C.c_uint32), ("sample_rate", C.c_float), ("auto_flags", C.c_uint32),
+                ("look_ahead_time", C.c_float), ("hold_time", C.c_float), ("pre_gain_db", C.c_float),
+                ("post_gain_db", C.c_float), ("threshold_db", C.c_float), ("ratio", C.c_float),
+                ("knee_db", C.c_float), ("attack_time", C.c_float), ("release_time", C.c_float)]
+
+
+(LIMITER_AUTO_KNEE, LIMITER_AUTO_ATTACK, LIMITER_AUTO_RELEASE, LIMITER_AUTO_POST_GAIN,
+ LIMITER_AUTO_DECLIP) = (1, 2, 4, 8, 16)
+
+
 def check(rc, what=""):
     if rc < 0:
         raise OalgpuError(f"{what} failed ({rc}): {lib.oalgpu_last_error().decode()}")
@@ -197,6 +209,22 @@ def check(rc, what=""):
 
 def device_count():
     return lib.oalgpu_device_count()
+
+
+def limiter_device_params(sample_rate, sample_type, dither_depth=0.0):
+    """The device limiter the reference builds for this output format: (enabled by default, LimiterParams)."""
+    lib.oalgpu_limiter_device_params.argtypes = [C.c_uint32, C.c_int, C.c_float, C.POINTER(LimiterParams)]
+    p = LimiterParams()
+    rc = check(lib.oalgpu_limiter_device_params(sample_rate, sample_type, dither_depth, C.byref(p)),
+               "oalgpu_limiter_device_params")
+    return bool(rc), p
+
+
+def limiter_look_ahead(params):
+    """The limiter's delay in samples (Compressor::getLookAhead)."""
+    lib.oalgpu_limiter_look_ahead.argtypes = [C.POINTER(LimiterParams)]
+    lib.oalgpu_limiter_look_ahead.restype = C.c_uint32
+    return int(lib.oalgpu_limiter_look_ahead(C.byref(params)))
 
 
 class Api:
@@ -648,6 +676,12 @@ class Scene:
         lib.oalgpu_set_output.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint32]
         check(lib.oalgpu_set_output(self.h, sample_type, dither_depth, dither_seed), "oalgpu_set_output")
         self._out_type = sample_type
+
+    def set_output_limiter(self, params):
+        """Installs a fresh output limiter (LimiterParams), or removes it (None)."""
+        lib.oalgpu_set_output_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterParams)]
+        check(lib.oalgpu_set_output_limiter(self.h, C.byref(params) if params is not None else None),
+              "oalgpu_set_output_limiter")
 
     def read_output(self, samples_to_do=BUFFER_LINE, frame_step=2):
         lib.oalgpu_read_output.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
