@@ -237,6 +237,28 @@ def test_scene_voice_mix_bit_exact(libs, mhr_paths, idx):
     assert_bit_equal(fa, fb, f"scene {idx}")
 
 
+import loop_edge_cases
+
+
+@pytest.mark.parametrize("mixed", [False, True], ids=["one_key", "mixed_keys"])
+@pytest.mark.parametrize("form", ["hrtf", "dry", "dry_sends"])
+@pytest.mark.parametrize("step", loop_edge_cases.STEPS)
+def test_loop_edge_scenes_bit_exact(libs, mhr_paths, step, form, mixed):
+    """Static voices at the edges of their loops (tests/loop_edge_cases.py): short loops, loop ends inside the source
+    window, positions at and past the loop end, one-shot voices at and past the buffer end, tiny buffers."""
+    ref, port = libs
+    fa, ia, _ = loop_edge_cases.run(ref, step, form, mhr_paths[-1], mixed=mixed)
+    fb, ib, _ = loop_edge_cases.run(port, step, form, mhr_paths[-1], mixed=mixed)
+    assert ia == ib, "integer voice state"
+    for k, (a, b) in enumerate(zip(fa, fb)):
+        assert_bit_equal(a, b, f"step {step} {form} update {k}")
+    if step == loop_edge_cases.FRAC_ONE:
+        fa, ia, _ = loop_edge_cases.run(ref, step, form, mhr_paths[-1], mixed=mixed, frac_zero=True)
+        fb, ib, _ = loop_edge_cases.run(port, step, form, mhr_paths[-1], mixed=mixed, frac_zero=True)
+        assert ia == ib
+        assert_bit_equal(np.concatenate(fa), np.concatenate(fb), "step 1.0, no fraction")
+
+
 @pytest.mark.parametrize("ir_size", [24, 32, 128])
 def test_other_hrir_lengths_bit_exact(libs, tmp_path, ir_size):
     """Data sets whose IrSize is not 64 (what tests/test_gpu_parity.py::test_hrir_lengths_other_than_64
