@@ -557,6 +557,24 @@ uint32_t oalgpu_limiter_look_ahead(const oalgpu_limiter_params *params);
  * Waits for the context's work in flight.  Parity with the reference is bounded, not bit-exact: the
  * kernel's logf / expf are the correctly rounded results, which glibc's are not everywhere. */
 int oalgpu_set_output_limiter(oalgpu_context *ctx, const oalgpu_limiter_params *params);
+/* ---- the stereo UHJ encoder: UhjPostProcess (alc/alu.cpp:300-311; UhjEncoderIIR / UhjEncoder<N>, core/uhjfilter.cpp) ----
+ * A stereo device's post-process for ALC_STEREO_UHJ_SOFT output: the first-order 2D dry bus is encoded into
+ * stereo-compatible 2-channel UHJ on the two real output lines.  The encoder reads the dry lines in the order W, X, Y
+ * (FuMa order, N3D scale); a caller sets this up as InitUhjPanning does, with
+ * oalgpu_context_set_ambi_map(index = {0, 3, 1}, scale = {1, 1, 1}).  Qualities in UhjQualityType order. */
+enum oalgpu_uhj_quality { OALGPU_UHJ_IIR = 0, OALGPU_UHJ_FIR256, OALGPU_UHJ_FIR512 };
+/* Host only.  The encoder's delay in samples (getDelay, what the reference adds to FixedLatency): 1 (IIR), 256
+ * (FIR-256), 384 (FIR-512); 0 for an invalid quality. */
+uint32_t oalgpu_uhj_encoder_delay(int quality);
+/* Installs the encoder with fresh (zero) state (quality >= 0) or removes it (quality < 0); off by default.  Only on a
+ * non-HRTF context with num_dry_channels == 3 and num_real_channels == 2, and not while a B-Format decoder is set
+ * (a device has one post-process; oalgpu_set_bformat_decoder likewise refuses while an encoder is set): otherwise
+ * OALGPU_ERR_INVALID with nothing changed.  It runs behind the effect slots and before the limiter of every update
+ * that post-processes, on the stream that runs the post-process (the real lines are the direct input it delays and
+ * adds to); oalgpu_read_dry, oalgpu_read_output and the limiter see the encoded lines.  Waits for the context's work
+ * in flight.  IIR is bit-identical to the reference; FIR-N applies the reference's phase-shift response as a direct
+ * FIR (the same filter as its segmented FFT convolution, to rounding). */
+int oalgpu_set_uhj_encoder(oalgpu_context *ctx, int quality);
 
 /* Device address of the bus block [dry+real lines | wet buses | hrtf accum], its length in
  * floats, and the stream it is produced on, for zero-copy consumers: the context's main stream for

@@ -760,6 +760,7 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
                 c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, D.numDry, c->decOut, samples_to_do);
             HIP_TRY(hipGetLastError());
         }
+        if(int rc = RunUhjEncoder(c, c->stream, samples_to_do)) return rc;     // (UhjPostProcess, alc/alu.cpp:300-311)
         if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
         if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
         return OALGPU_OK;
@@ -926,6 +927,7 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
             c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, L.numDry, c->decOut, samples_to_do);
         HIP_TRY(hipGetLastError());
     }
+    if(post_process && !L.hrtf) { if(int rc = RunUhjEncoder(c, c->postStream, samples_to_do)) return rc; }
     if(post_process) { if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc; }
     if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->postStream)); c->timed = true; }
     if(!postDoneBound) HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));

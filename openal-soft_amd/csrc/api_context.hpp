@@ -202,6 +202,10 @@ struct oalgpu_context {
     bool limOn{false};
     LimiterConsts lim{};
     DevBuf<float> limState;
+    // the stereo UHJ encoder (oalgpu_set_uhj_encoder; RunUhjEncoder, the post-process of a 3-dry / 2-real context): its quality
+    // (-1: none), FIR taps and device state
+    int uhjQuality{-1};
+    DevBuf<float> uhjTaps, uhjState;
     DevBuf<unsigned char> pcm;
     // HRTF store
     DevBuf<float> hFieldDist, hCoeffs;
@@ -358,6 +362,7 @@ int AllocStreamRows(oalgpu_context *c);
 uint32_t DeviceComputeUnits(int device);
 int JoinPost(oalgpu_context *c);
 int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip
+int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
 bool HostStoresReachDevice(oalgpu_context *c);                     // api_voices.hip
 int AllocBufferHandle(oalgpu_context *c, uint32_t *out);           // api_voices.hip
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip

@@ -184,6 +184,8 @@ int oalgpu_set_bformat_decoder(oalgpu_context *c, uint32_t num_out, const float 
     if(int rc = UseCtx(c)) return rc;
     if(int rc = oalgpu_sync(c)) return rc;
     if(num_out == 0 || !coeffs_hf) { c->decOn = false; return OALGPU_OK; }
+    if(c->uhjQuality >= 0)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context post-processes with its UHJ encoder");
     if(num_out > c->L.numReal || num_out > 32u)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: more output channels than real output lines");
     if(coeffs_lf && !(xover_norm > 0.0f && xover_norm < 0.5f))
@@ -274,6 +276,59 @@ int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
     if(!c->limOn) return OALGPU_OK;
     const DeviceLayout &L = c->L;
     LaunchLimiter(s, L.numReal ? L.bus + size_t{L.numDry} * kLine : L.bus, samplesToDo, c->lim, c->limState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+/* The stereo UHJ encoder (UhjPostProcess, alc/alu.cpp:300-311): the quality's taps (host/uhj_params.cpp), a fresh state, and
+ * from the next update on the encode behind every post-process (RunUhjEncoder) */
+uint32_t oalgpu_uhj_encoder_delay(int quality) { return UhjEncoderDelay(quality); }
+
+int oalgpu_set_uhj_encoder(oalgpu_context *c, int quality)
+{
+    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
+    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
+    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
+    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: null context");
+    if(quality >= 0)
+    {
+        if(UhjEncoderDelay(quality) == 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: not a UHJ quality");
+        if(c->L.hrtf)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: an HRTF context post-processes with MixDirectHrtf");
+        if(c->L.numDry != 3 || c->L.numReal != 2)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: needs three dry lines (W, X, Y) and two real output lines");
+        if(c->decOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its B-Format decoder");
+    }
+    // the kernels of the updates in flight are through with the old state before it goes
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->uhjQuality = -1;
+    if(quality >= 0)
+    {
+        if(const uint32_t len = UhjFirLength(quality))
+        {
+            const std::vector<float> taps = UhjFirTaps(len);
+            HIP_TRY(c->uhjTaps.alloc(taps.size()));
+            HIP_TRY(c->uhjTaps.upload(taps.data(), taps.size()));
+        }
+        const std::vector<float> init(UhjStateFloats(quality), 0.0f);
+        HIP_TRY(c->uhjState.alloc(init.size()));
+        HIP_TRY(c->uhjState.upload(init.data(), init.size()));
+        c->uhjQuality = quality;
+    }
+    return OALGPU_OK;
+}
+
+// UhjEncoder*::encode behind the update's effect slots, on the stream that runs the post-process: dry lines 0-2 (W, X, Y) in,
+// the two real output lines (FrontLeft, FrontRight) delayed and added to
+int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(c->uhjQuality < 0) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    float *left = L.bus + size_t{L.numDry} * kLine;
+    LaunchUhjEncode(s, c->uhjQuality, left, left + kLine, L.bus, L.bus + kLine, L.bus + 2 * kLine, samplesToDo, c->uhjTaps.p,
+        c->uhjState.p);
     HIP_TRY(hipGetLastError());
     return OALGPU_OK;
 }

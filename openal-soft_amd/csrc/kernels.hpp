@@ -8,6 +8,7 @@
 #include "dev_resample.hpp"
 #include "dev_voice.hpp"
 #include "../host/limiter_params.hpp"
+#include "../host/uhj_params.hpp"
 
 namespace oalgpu {
 
@@ -332,6 +333,11 @@ void LaunchWriteSamples(hipStream_t s, int sampleType, const float *lines, uint3
 void LaunchLimiter(hipStream_t s, float *lines, uint32_t n, const LimiterConsts &k, float *state);
 size_t LimiterStateFloats(uint32_t nch);
 constexpr size_t kLimiterHoldHistory = 16u + 1024u;      // where the hold's history starts in the state
+// ---- launcher (uhj_kernels.hip): the stereo UHJ encoder of `quality` (kUhj*) from the dry lines w, x, y onto left / right (one
+// workgroup); taps: FIR-N's UhjFirTaps (unused for IIR); state: UhjStateFloats(quality) floats, zero when fresh ----
+void LaunchUhjEncode(hipStream_t s, int quality, float *left, float *right, const float *w, const float *x, const float *y,
+    uint32_t n, const float *taps, float *state);
+size_t UhjStateFloats(int quality);
 // ---- launcher (effects_kernels.hip): equalizer / modulator / echo / dedicated, one workgroup per instance ----
 constexpr uint32_t kFxMaxIn = 16;
 struct FxState {                       // device-resident per instance

@@ -227,6 +227,16 @@ def limiter_look_ahead(params):
     return int(lib.oalgpu_limiter_look_ahead(C.byref(params)))
 
 
+(UHJ_IIR, UHJ_FIR256, UHJ_FIR512) = range(3)                 # enum oalgpu_uhj_quality (UhjQualityType order)
+
+
+def uhj_encoder_delay(quality):
+    """The UHJ encoder's delay in samples (getDelay): 1, 256 or 384; 0 for an invalid quality."""
+    lib.oalgpu_uhj_encoder_delay.argtypes = [C.c_int]
+    lib.oalgpu_uhj_encoder_delay.restype = C.c_uint32
+    return int(lib.oalgpu_uhj_encoder_delay(quality))
+
+
 class Api:
     """Per-call mirrors + table access, with the same method names as tests/oracle_lib.OracleLib
     so the parity tests can drive oracle and product through one code path."""
@@ -682,6 +692,11 @@ class Scene:
         lib.oalgpu_set_output_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterParams)]
         check(lib.oalgpu_set_output_limiter(self.h, C.byref(params) if params is not None else None),
               "oalgpu_set_output_limiter")
+
+    def set_uhj_encoder(self, quality):
+        """Installs a fresh stereo UHJ encoder (UHJ_IIR, UHJ_FIR256, UHJ_FIR512) as the post-process, or removes it (None)."""
+        lib.oalgpu_set_uhj_encoder.argtypes = [C.c_void_p, C.c_int]
+        check(lib.oalgpu_set_uhj_encoder(self.h, -1 if quality is None else quality), "oalgpu_set_uhj_encoder")
 
     def read_output(self, samples_to_do=BUFFER_LINE, frame_step=2):
         lib.oalgpu_read_output.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
