@@ -575,6 +575,42 @@ uint32_t oalgpu_uhj_encoder_delay(int quality);
  * in flight.  IIR is bit-identical to the reference; FIR-N applies the reference's phase-shift response as a direct
  * FIR (the same filter as its segmented FFT convolution, to rounding). */
 int oalgpu_set_uhj_encoder(oalgpu_context *ctx, int quality);
+/* ---- the front stabilizer: StablizerPostProcess (alc/alu.cpp:329-405; core/front_stablizer.h; CreateStablizer,
+ * alc/panning.cpp:160-172) ----
+ * The post-process of a decoded speaker layout with a front-centre speaker when `front-stablizer` is on.  It owns the B-Format
+ * decoder: the direct FrontLeft / FrontRight signal is moved out as mid and side, the dry lines are decoded, the decoded mid is
+ * band-split and panned partly onto FrontCenter (the low band 1/3 of the way, the high band 1/4), and every real line goes
+ * through the splitter's all-pass so that the phases stay aligned. */
+typedef struct oalgpu_stabilizer_params {
+    uint32_t left, right, center;   /* real output line of FrontLeft / FrontRight / FrontCenter (RealOut.ChannelIndex) */
+    float    xover_norm;            /* MidFilter.init's argument: 5000 / sample rate in the reference */
+} oalgpu_stabilizer_params;
+/* Host only.  What the stabilizer's kernel is given for xover_norm, out[5]: BandSplitter::init's coefficient, then mid_lf, mid_hf,
+ * center_lf, center_hf (cosf / sinf of the host libm, as the reference computes them).  OALGPU_ERR_INVALID unless
+ * 0 < xover_norm < 0.5. */
+int oalgpu_front_stabilizer_constants(float xover_norm, float *out);
+/* Installs the stabilizer with fresh (zero) filter state, or removes it (params == NULL); off by default.  Only on a non-HRTF
+ * context that has a B-Format decoder set and no UHJ encoder, with left, right, center three different lines < num_real_channels
+ * and 0 < xover_norm < 0.5: otherwise OALGPU_ERR_INVALID with nothing changed.  While it is set, oalgpu_set_bformat_decoder may
+ * replace the decoder's matrices (the stabilizer's filter state is kept) but refuses to remove the decoder.  It runs around the
+ * decode of every update that post-processes, on the stream that runs the post-process, before the limiter; bit-identical to the
+ * reference given the same decoded feeds.  Waits for the context's work in flight. */
+int oalgpu_set_front_stabilizer(oalgpu_context *ctx, const oalgpu_stabilizer_params *params);
+/* ---- speaker distance compensation: ApplyDistanceComp (alc/alu.cpp:2276-2307; InitDistanceComp, alc/panning.cpp:301-371) ----
+ * Host only: InitDistanceComp's arithmetic for n (1..32) channels; distances in metres, <= 0 = channel not compensated:
+ * delay = floor((maxdist - d) * (rate / 343.3f) + 0.5f) clamped to 1023, gain = d / maxdist, in float; delay 0 / gain 1 for
+ * d <= 0.  Returns 1 if any delay is non-zero (the reference's `total > 0`: it then creates ChannelDelays), 0 if not
+ * (maxdist <= 0 included), OALGPU_ERR_INVALID on bad arguments. */
+int oalgpu_distance_comp_from_distances(uint32_t sample_rate, const float *distances, uint32_t n,
+                                        uint32_t *delays, float *gains);
+/* Per output line (the real lines, or the dry lines of a context without any: the limiter's line set) a delay in samples
+ * (<= 1023 = DistanceComp::MaxDelay - 1) and a gain, with fresh (zero) delay lines; n = 0 or a NULL array removes; off by
+ * default.  Non-HRTF contexts only, n <= the number of output lines: otherwise OALGPU_ERR_INVALID with nothing changed.  From the
+ * next update that post-processes on, out[t] = gain * x[t - delay] directly behind the limiter, the last `delay` inputs carried
+ * across updates: oalgpu_read_dry, oalgpu_read_output (dither and Write<T> behind it) and oalgpu_read_output_async see the
+ * compensated lines.  As in the reference a line with delay 0 is left alone: its gain is NOT applied.  Waits for the context's
+ * work in flight. */
+int oalgpu_set_distance_comp(oalgpu_context *ctx, uint32_t n, const uint32_t *delays, const float *gains);
 
 /* Device address of the bus block [dry+real lines | wet buses | hrtf accum], its length in
  * floats, and the stream it is produced on, for zero-copy consumers: the context's main stream for

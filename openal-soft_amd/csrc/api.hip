@@ -756,12 +756,16 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
         if(c->decOn)
         {
             const DeviceLayout &D = c->L;
+            // (StablizerPostProcess, alc/alu.cpp:329-405: the stabilizer owns the decode; both calls return at once without one)
+            if(int rc = RunStabilizerSplit(c, c->stream, samples_to_do)) return rc;
             LaunchBFormatDecode(c->stream, c->exact, D.bus + size_t{D.numDry} * kLine, D.bus, c->decSplit.p, c->decBands.p,
                 c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, D.numDry, c->decOut, samples_to_do);
             HIP_TRY(hipGetLastError());
+            if(int rc = RunStabilizer(c, c->stream, samples_to_do)) return rc;
         }
         if(int rc = RunUhjEncoder(c, c->stream, samples_to_do)) return rc;     // (UhjPostProcess, alc/alu.cpp:300-311)
         if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
+        if(int rc = RunDistanceComp(c, c->stream, samples_to_do)) return rc;   // (ApplyDistanceComp, alc/alu.cpp:2449-2450)
         if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
         return OALGPU_OK;
     }
@@ -923,12 +927,15 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
     else c->lastPostEvent = c->evPostDone;
     if(post_process && !L.hrtf && c->decOn)
     {   // DeviceBase::Process(AmbiDecPostProcess), alc/alu.cpp:282-287: dry lines -> speaker feeds
+        if(int rc = RunStabilizerSplit(c, c->postStream, samples_to_do)) return rc;      // (StablizerPostProcess: see oalgpu_post_process)
         LaunchBFormatDecode(c->postStream, c->exact, L.bus + size_t{L.numDry} * kLine, L.bus, c->decSplit.p, c->decBands.p,
             c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, L.numDry, c->decOut, samples_to_do);
         HIP_TRY(hipGetLastError());
+        if(int rc = RunStabilizer(c, c->postStream, samples_to_do)) return rc;
     }
     if(post_process && !L.hrtf) { if(int rc = RunUhjEncoder(c, c->postStream, samples_to_do)) return rc; }
     if(post_process) { if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc; }
+    if(post_process && !L.hrtf) { if(int rc = RunDistanceComp(c, c->postStream, samples_to_do)) return rc; }
     if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->postStream)); c->timed = true; }
     if(!postDoneBound) HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));
     c->postPending = true;

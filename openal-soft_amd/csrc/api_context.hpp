@@ -206,6 +206,17 @@ struct oalgpu_context {
     // (-1: none), FIR taps and device state
     int uhjQuality{-1};
     DevBuf<float> uhjTaps, uhjState;
+    // the front stabilizer (oalgpu_set_front_stabilizer; RunStabilizerSplit / RunStabilizer around the B-Format decode): the real
+    // lines of FrontLeft / FrontRight / FrontCenter, its constants and device state
+    bool stabOn{false};
+    uint32_t stabLeft{0}, stabRight{0}, stabCenter{0};
+    StabilizerConsts stab{};
+    DevBuf<float> stabState;
+    // speaker distance compensation (oalgpu_set_distance_comp; RunDistanceComp behind the limiter of non-HRTF contexts): per
+    // output line its delay and gain, and the delay lines
+    uint32_t distLines{0};
+    DevBuf<uint32_t> distDelays;
+    DevBuf<float> distGains, distHist;
     DevBuf<unsigned char> pcm;
     // HRTF store
     DevBuf<float> hFieldDist, hCoeffs;
@@ -363,6 +374,9 @@ uint32_t DeviceComputeUnits(int device);
 int JoinPost(oalgpu_context *c);
 int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip
 int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
+int RunStabilizerSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip (in front of the decode)
+int RunStabilizer(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);  // api_output.hip (behind the decode)
+int RunDistanceComp(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
 bool HostStoresReachDevice(oalgpu_context *c);                     // api_voices.hip
 int AllocBufferHandle(oalgpu_context *c, uint32_t *out);           // api_voices.hip
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip

@@ -183,6 +183,8 @@ int oalgpu_set_bformat_decoder(oalgpu_context *c, uint32_t num_out, const float 
     if(c->L.hrtf) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: an HRTF context post-processes with MixDirectHrtf");
     if(int rc = UseCtx(c)) return rc;
     if(int rc = oalgpu_sync(c)) return rc;
+    if((num_out == 0 || !coeffs_hf) && c->stabOn)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context's front stabilizer decodes with it (remove the stabilizer first)");
     if(num_out == 0 || !coeffs_hf) { c->decOn = false; return OALGPU_OK; }
     if(c->uhjQuality >= 0)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context post-processes with its UHJ encoder");
@@ -329,6 +331,127 @@ int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
     float *left = L.bus + size_t{L.numDry} * kLine;
     LaunchUhjEncode(s, c->uhjQuality, left, left + kLine, L.bus, L.bus + kLine, L.bus + 2 * kLine, samplesToDo, c->uhjTaps.p,
         c->uhjState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+/* The front stabilizer (StablizerPostProcess, alc/alu.cpp:329-405; CreateStablizer, alc/panning.cpp:160-172): the constants
+ * (host/stabilizer_params.cpp), a fresh state, and from the next update on RunStabilizerSplit / RunStabilizer around the decode
+ * of every post-process */
+int oalgpu_front_stabilizer_constants(float xover_norm, float *out)
+{
+    StabilizerConsts k{};
+    if(!out || !StabilizerDerive(xover_norm, &k))
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_front_stabilizer_constants: needs 0 < xover_norm < 0.5");
+    out[0] = k.coeff; out[1] = k.midLf; out[2] = k.midHf; out[3] = k.centerLf; out[4] = k.centerHf;
+    return OALGPU_OK;
+}
+
+int oalgpu_set_front_stabilizer(oalgpu_context *c, const oalgpu_stabilizer_params *params)
+{
+    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
+    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
+    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
+    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: null context");
+    StabilizerConsts k{};
+    if(params)
+    {
+        if(c->L.hrtf)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: an HRTF context post-processes with MixDirectHrtf");
+        if(c->uhjQuality >= 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its UHJ encoder");
+        if(!c->decOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: needs a B-Format decoder (oalgpu_set_bformat_decoder)");
+        const uint32_t nr = c->L.numReal;
+        if(nr > 32u || params->left >= nr || params->right >= nr || params->center >= nr || params->left == params->right
+            || params->left == params->center || params->right == params->center)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: left, right and center are three different real output lines");
+        if(!StabilizerDerive(params->xover_norm, &k))
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: needs 0 < xover_norm < 0.5");
+    }
+    // the kernels of the updates in flight are through with the old state before it goes
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->stabOn = false;
+    if(params)
+    {
+        const std::vector<float> init(kStabilizerStateFloats, 0.0f);
+        HIP_TRY(c->stabState.alloc(init.size()));
+        HIP_TRY(c->stabState.upload(init.data(), init.size()));
+        c->stab = k;
+        c->stabLeft = params->left; c->stabRight = params->right; c->stabCenter = params->center;
+        c->stabOn = true;
+    }
+    return OALGPU_OK;
+}
+
+// in front of the decode: the direct L / R signal moves out of the stabilizer's way (alu.cpp:339-348)
+int RunStabilizerSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(!c->stabOn) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    LaunchStabilizerSplit(s, L.bus + size_t{L.numDry} * kLine, c->stabLeft, c->stabRight, samplesToDo, c->stabState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+// behind the decode: the band split of the decoded mid, the all-passes, the combine (alu.cpp:353-404)
+int RunStabilizer(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(!c->stabOn) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    LaunchStabilizer(s, L.bus + size_t{L.numDry} * kLine, L.numReal, c->stabLeft, c->stabRight, c->stabCenter, samplesToDo, c->stab,
+        c->stabState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+/* Speaker distance compensation (ApplyDistanceComp, alc/alu.cpp:2276-2307; InitDistanceComp, alc/panning.cpp:301-371): per
+ * output line a delay and a gain, fresh (zero) delay lines, and from the next update on RunDistanceComp behind the limiter */
+int oalgpu_distance_comp_from_distances(uint32_t sample_rate, const float *distances, uint32_t n, uint32_t *delays, float *gains)
+{
+    if(sample_rate == 0 || !distances || !delays || !gains || n == 0 || n > 32u)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_distance_comp_from_distances: bad arguments");
+    return DistanceCompDerive(sample_rate, distances, n, delays, gains) ? 1 : 0;
+}
+
+int oalgpu_set_distance_comp(oalgpu_context *c, uint32_t n, const uint32_t *delays, const float *gains)
+{
+    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
+    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
+    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
+    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: null context");
+    const bool set = n != 0 && delays && gains;
+    if(set)
+    {
+        if(c->L.hrtf)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: an HRTF context has no speaker distances to compensate");
+        if(n > (c->L.numReal ? c->L.numReal : c->L.numDry))
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: more channels than the context has output lines");
+        for(uint32_t i = 0; i < n; ++i)
+            if(delays[i] > kDistCompMaxDelay)
+                return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: a delay of more than 1023 samples");
+    }
+    // the kernels of the updates in flight are through with the old delay lines before they go
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->distLines = 0;
+    if(set)
+    {
+        HIP_TRY(c->distDelays.alloc(n)); HIP_TRY(c->distDelays.upload(delays, n));
+        HIP_TRY(c->distGains.alloc(n)); HIP_TRY(c->distGains.upload(gains, n));
+        const std::vector<float> init(size_t{n} * kLine, 0.0f);
+        HIP_TRY(c->distHist.alloc(init.size())); HIP_TRY(c->distHist.upload(init.data(), init.size()));
+        c->distLines = n;
+    }
+    return OALGPU_OK;
+}
+
+// ApplyDistanceComp behind the limiter, on the stream that ran it (alc/alu.cpp:2449-2450), over the limiter's line set
+int RunDistanceComp(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(!c->distLines) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    LaunchDistanceComp(s, L.numReal ? L.bus + size_t{L.numDry} * kLine : L.bus, c->distLines, samplesToDo, c->distDelays.p,
+        c->distGains.p, c->distHist.p);
     HIP_TRY(hipGetLastError());
     return OALGPU_OK;
 }

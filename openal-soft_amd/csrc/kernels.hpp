@@ -9,6 +9,7 @@
 #include "dev_voice.hpp"
 #include "../host/limiter_params.hpp"
 #include "../host/uhj_params.hpp"
+#include "../host/stabilizer_params.hpp"
 
 namespace oalgpu {
 
@@ -338,6 +339,19 @@ constexpr size_t kLimiterHoldHistory = 16u + 1024u;      // where the hold's his
 void LaunchUhjEncode(hipStream_t s, int quality, float *left, float *right, const float *w, const float *x, const float *y,
     uint32_t n, const float *taps, float *state);
 size_t UhjStateFloats(int quality);
+// ---- launchers (stabilizer_kernels.hip): the front stabilizer around LaunchBFormatDecode (StablizerPostProcess).  Split, in front
+// of the decode: mid = L + R and side = L - R of the real lines lidx / ridx into the state's scratch, both lines zeroed.
+// Stabilizer, behind it: the band split of the decoded mid, the all-pass of every real line, the combine (one workgroup).
+// state: kStabilizerStateFloats floats, zero when fresh ----
+constexpr size_t kStabilizerScratch = 64;                       // where mid[1024] | side[1024] start in the state
+constexpr size_t kStabilizerStateFloats = kStabilizerScratch + 2 * kLine;
+void LaunchStabilizerSplit(hipStream_t s, float *real, uint32_t lidx, uint32_t ridx, uint32_t n, float *state);
+void LaunchStabilizer(hipStream_t s, float *real, uint32_t numReal, uint32_t lidx, uint32_t ridx, uint32_t cidx, uint32_t n,
+    const StabilizerConsts &k, float *state);
+// ---- launcher (stabilizer_kernels.hip): ApplyDistanceComp over nlines lines in place, one workgroup per line; delays / gains per
+// line (device), hist: nlines x 1024 floats, zero when fresh ----
+void LaunchDistanceComp(hipStream_t s, float *lines, uint32_t nlines, uint32_t n, const uint32_t *delays, const float *gains,
+    float *hist);
 // ---- launcher (effects_kernels.hip): equalizer / modulator / echo / dedicated, one workgroup per instance ----
 constexpr uint32_t kFxMaxIn = 16;
 struct FxState {                       // device-resident per instance

@@ -237,6 +237,34 @@ def uhj_encoder_delay(quality):
     return int(lib.oalgpu_uhj_encoder_delay(quality))
 
 
+class StabilizerParams(C.Structure):
+    """oalgpu_stabilizer_params"""
+    _fields_ = [("left", C.c_uint32), ("right", C.c_uint32), ("center", C.c_uint32), ("xover_norm", C.c_float)]
+
+
+def front_stabilizer_constants(xover_norm):
+    """The stabilizer kernel's constants for xover_norm as float32[5]: BandSplitter::init's coefficient, mid_lf, mid_hf,
+    center_lf, center_hf."""
+    out = np.zeros(5, np.float32)
+    lib.oalgpu_front_stabilizer_constants.argtypes = [C.c_float, f32p]
+    check(lib.oalgpu_front_stabilizer_constants(xover_norm, _fp(out)), "oalgpu_front_stabilizer_constants")
+    return out
+
+
+def distance_comp_from_distances(sample_rate, distances):
+    """InitDistanceComp's arithmetic: -> (delays uint32[n], gains float32[n], any), any = some delay is non-zero (the
+    reference then creates ChannelDelays)."""
+    d = np.ascontiguousarray(distances, np.float32)
+    delays = np.zeros(d.size, np.uint32)
+    gains = np.zeros(d.size, np.float32)
+    lib.oalgpu_distance_comp_from_distances.argtypes = [C.c_uint32, f32p, C.c_uint32, C.POINTER(C.c_uint32), f32p]
+    rc = lib.oalgpu_distance_comp_from_distances(sample_rate, _fp(d), d.size, delays.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 _fp(gains))
+    if rc < 0:
+        check(rc, "oalgpu_distance_comp_from_distances")
+    return delays, gains, bool(rc)
+
+
 class Api:
     """Per-call mirrors + table access, with the same method names as tests/oracle_lib.OracleLib
     so the parity tests can drive oracle and product through one code path."""
@@ -697,6 +725,29 @@ class Scene:
         """Installs a fresh stereo UHJ encoder (UHJ_IIR, UHJ_FIR256, UHJ_FIR512) as the post-process, or removes it (None)."""
         lib.oalgpu_set_uhj_encoder.argtypes = [C.c_void_p, C.c_int]
         check(lib.oalgpu_set_uhj_encoder(self.h, -1 if quality is None else quality), "oalgpu_set_uhj_encoder")
+
+    def set_front_stabilizer(self, left, right=None, center=None, xover_norm=5000.0 / 48000.0):
+        """Installs a fresh front stabilizer around the B-Format decode (left / right / center: the real output lines of
+        FrontLeft / FrontRight / FrontCenter), or removes it (left None)."""
+        lib.oalgpu_set_front_stabilizer.argtypes = [C.c_void_p, C.POINTER(StabilizerParams)]
+        if left is None:
+            check(lib.oalgpu_set_front_stabilizer(self.h, None), "oalgpu_set_front_stabilizer")
+            return
+        params = StabilizerParams(left, right, center, xover_norm)
+        check(lib.oalgpu_set_front_stabilizer(self.h, C.byref(params)), "oalgpu_set_front_stabilizer")
+
+    def set_distance_comp(self, delays, gains=None):
+        """Installs speaker distance compensation with fresh delay lines (per output line a delay in samples <= 1023 and a
+        gain), or removes it (delays None)."""
+        u32p = C.POINTER(C.c_uint32)
+        lib.oalgpu_set_distance_comp.argtypes = [C.c_void_p, C.c_uint32, u32p, f32p]
+        if delays is None:
+            check(lib.oalgpu_set_distance_comp(self.h, 0, None, None), "oalgpu_set_distance_comp")
+            return
+        d = np.ascontiguousarray(delays, np.uint32)
+        g = np.ascontiguousarray(gains, np.float32)
+        assert d.ndim == 1 and d.shape == g.shape
+        check(lib.oalgpu_set_distance_comp(self.h, d.size, d.ctypes.data_as(u32p), _fp(g)), "oalgpu_set_distance_comp")
 
     def read_output(self, samples_to_do=BUFFER_LINE, frame_step=2):
         lib.oalgpu_read_output.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
