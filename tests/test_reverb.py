@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from reverb_cases import CASES, FULL_CASES, SEED, wet_input, BUFFER_LINE, out_init
+from reverb_cases import (CASES, FULL_CASES, SEED, wet_input, BUFFER_LINE, out_init, RATES, RATE_MATRIX, RATE_IDS,
+                          rate_seed, check_reach, check_longest_delays)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 IDS = [c[0] for c in CASES]
@@ -77,6 +78,37 @@ def test_port_matches_reference(name, schedule):
         assert np.array_equal(bits(a), bits(b)), (name, u, np.abs(a - b).max())
         energy += float(np.abs(a[:, 7:]).sum())
     assert energy > 1.0
+    ref.close(); port_.close()
+
+
+@needs_ref
+@pytest.mark.parametrize("name,schedule,rate", RATE_MATRIX, ids=RATE_IDS)
+def test_port_matches_reference_at_rate(name, schedule, rate):
+    """The same at the device rates of RATES, over CASES and RATE_CASES: late sub-blocks bounded by mLate.Offset[0]
+    (below 256 samples at 8000-22050 Hz and density 0), all-pass chunks of 3 and 6 samples, the 0.49 cap of hf0norm,
+    the longest delays.  Each case proves from the reference's parameter block that it reaches what it is for
+    (reverb_cases.check_reach).  The GPU tests fall back on the restatement where the reference is absent, so it has to
+    be right at these rates too."""
+    lib = ol.load("ref")
+    ref = lib.make_reverb(4, rate)
+    port_ = ol.load("port").make_reverb(4, rate)
+    x = wet_input(rate_seed(name, rate), len(schedule))
+    energy, k, outs = 0.0, 0, []
+    for u, st in enumerate(schedule):
+        if st["props"] is not None:
+            before = ref.get_params().pipeline_state
+            ref.update(ol.ReverbProps.make(**st["props"]), st["slot_gain"])
+            check_reach(lib, ol.ReverbProps, name, rate, k, st, ref.get_params(), before)
+            port_.set_params(ref.get_params())
+            k += 1
+        a, b = out_init(4), out_init(4)
+        ref.process_n(x[u], a, st["n"])
+        port_.process_n(x[u], b, st["n"])
+        assert np.array_equal(bits(a), bits(b)), (name, rate, u, np.abs(a - b).max())
+        energy += float(np.abs(a[:, 7:]).sum())
+        outs.append(a)
+    assert energy > 1.0, (name, rate, energy)
+    check_longest_delays(name, rate, schedule, outs, ref.get_params())
     ref.close(); port_.close()
 
 
@@ -176,6 +208,85 @@ def test_host_bookkeeping_matches_reference(name, schedule):
         g.skip(st["n"])
         assert block_bytes(g.get_params()) == ref.get_params().as_bytes(), (name, u, "after process")
     ref.close(); g.close()
+
+
+@needs_ref
+@pytest.mark.parametrize("name,schedule,rate", RATE_MATRIX, ids=RATE_IDS)
+def test_host_bookkeeping_matches_reference_at_rate(name, schedule, rate):
+    """The product's host half at the device rates of RATES: the parameter block byte for byte before and after every
+    process() of CASES and RATE_CASES."""
+    oalgpu = _product()
+    ref = ol.load("ref").make_reverb(4, rate)
+    g = oalgpu.Reverb(4, rate, device=-1)
+    x = wet_input(rate_seed(name, rate), len(schedule))
+    for u, st in enumerate(schedule):
+        if st["props"] is not None:
+            ref.update(ol.ReverbProps.make(**st["props"]), st["slot_gain"])
+            g.update(oalgpu.ReverbProps.make(**st["props"]), st["slot_gain"])
+        assert block_bytes(g.get_params()) == ref.get_params().as_bytes(), (name, rate, u, "before process")
+        ref.process_n(x[u], out_init(4), st["n"])
+        g.skip(st["n"])
+        assert block_bytes(g.get_params()) == ref.get_params().as_bytes(), (name, rate, u, "after process")
+    ref.close(); g.close()
+
+
+@needs_ref
+def test_host_line_lengths_match_reference_at_rates():
+    oalgpu = _product()
+    for rate in RATES:
+        a = ol.load("ref").make_reverb(4, rate)
+        b = oalgpu.Reverb(4, rate, device=-1)
+        assert a.line_lengths() == b.line_lengths(), rate
+        a.close(); b.close()
+
+
+def test_creation_limits_without_a_device():
+    """A parameter-only instance takes any rate from 8000 Hz up (96000 and 192000 are relied on above); below that
+    oalgpu_reverb_create refuses."""
+    oalgpu = _product()
+    for rate in (8000, 96000, 192000):
+        g = oalgpu.Reverb(4, rate, device=-1)
+        g.update(oalgpu.ReverbProps.make())
+        g.close()
+    with pytest.raises(RuntimeError):
+        oalgpu.Reverb(4, 7999, device=-1)
+
+
+@needs_ref
+def test_host_update_random_props_match_reference_at_rates():
+    """More trials of the test below, drawn over RATES and 48000: at the low rates hf_reference / rate runs into the
+    0.49 cap for most of its legal range (above 3920 Hz at 8000 Hz), and half the trials draw hf_reference from the top
+    of the range and lf_reference from its ends."""
+    oalgpu = _product()
+    rng = np.random.default_rng(2025)
+    rates = RATES + (48000,)
+    for trial in range(70):
+        rate = rates[trial % len(rates)]
+        ref = ol.load("ref").make_reverb(4, rate)
+        g = oalgpu.Reverb(4, rate, device=-1)
+        edge = (trial // len(rates)) % 2 == 1
+        base = dict(density=rng.uniform(0, 1) ** 3, diffusion=rng.uniform(0, 1), decay_time=rng.uniform(0.1, 20),
+                    decay_hf_ratio=rng.uniform(0.1, 2), decay_lf_ratio=rng.uniform(0.1, 2),
+                    modulation_time=rng.uniform(0.04, 4), modulation_depth=rng.uniform(0, 1),
+                    hf_reference=rng.uniform(0.45 * rate, 20000) if edge and 0.45 * rate < 20000 else rng.uniform(1000, 20000),
+                    lf_reference=float(rng.choice([20.0, 1000.0])) if edge else rng.uniform(20, 1000),
+                    decay_hf_limit=int(rng.integers(0, 2)), air_absorption_gain_hf=rng.uniform(0.892, 1.0))
+        for u in range(4):
+            kw = dict(base)
+            kw.update(gain=rng.uniform(0, 1), gain_hf=rng.uniform(0, 1), gain_lf=rng.uniform(0, 1),
+                      reflections_gain=rng.uniform(0, 3.16), reflections_delay=rng.uniform(0, 0.3),
+                      late_reverb_gain=rng.uniform(0, 10), late_reverb_delay=rng.uniform(0, 0.1),
+                      reflections_pan=tuple(rng.uniform(-1, 1, 3)), late_reverb_pan=tuple(rng.uniform(-1, 1, 3)))
+            if u == 2:
+                kw["density"] = 0.0 if trial % 2 else rng.uniform(0, 1)       # forces a second full update
+                base = {k: kw[k] for k in base}
+            slot_gain = float(rng.uniform(0, 1))
+            ref.update(ol.ReverbProps.make(**kw), slot_gain)
+            g.update(oalgpu.ReverbProps.make(**kw), slot_gain)
+            assert block_bytes(g.get_params()) == ref.get_params().as_bytes(), (trial, rate, u)
+            ref.process_n(np.zeros((4, BUFFER_LINE), np.float32), out_init(4), BUFFER_LINE)
+            g.skip(BUFFER_LINE)
+        ref.close(); g.close()
 
 
 @needs_ref
