@@ -575,6 +575,43 @@ uint32_t oalgpu_uhj_encoder_delay(int quality);
  * in flight.  IIR is bit-identical to the reference; FIR-N applies the reference's phase-shift response as a direct
  * FIR (the same filter as its segmented FFT convolution, to rounding). */
 int oalgpu_set_uhj_encoder(oalgpu_context *ctx, int quality);
+/* ---- the stereo TSME encoder: TsmePostProcess (alc/alu.cpp:314-327; TsmeEncoderIIR / TsmeEncoder<N>, core/tsmefilter.cpp) ----
+ * A stereo device's post-process for `stereo-encoding = tsme`: the first-order 3D dry bus is encoded into two
+ * stereo-compatible channels ("tetraphonic surround matrix encoding") on the two real output lines.  The encoder reads four
+ * dry lines in ACN order (W, Y, Z, X) at N3D scale; a caller sets this up as InitTsmePanning does, with
+ * oalgpu_context_set_ambi_map(index = {0, 1, 2, 3}, scale = {1, 1, 1, 1}) and two real lines.  Qualities in TsmeQualityType
+ * order. */
+enum oalgpu_tsme_quality { OALGPU_TSME_IIR = 0, OALGPU_TSME_FIR256, OALGPU_TSME_FIR512 };
+/* Host only.  The encoder's delay in samples (getDelay): 1 (IIR), 256 (FIR-256), 384 (FIR-512); 0 for an invalid quality. */
+uint32_t oalgpu_tsme_encoder_delay(int quality);
+/* Installs the encoder with fresh (zero) state (quality >= 0) or removes it (quality < 0); off by default.  Only on a
+ * non-HRTF context with num_dry_channels == 4 and num_real_channels == 2, and not while a B-Format decoder, a UHJ encoder, a
+ * front stabilizer or a crossfeed is set (a device has one post-process; their setters likewise refuse while this encoder is
+ * set): otherwise OALGPU_ERR_INVALID with nothing changed.  It runs where the UHJ encoder runs: behind the effect slots and
+ * before the limiter of every update that post-processes, on the stream that runs the post-process (the real lines are the
+ * direct input it delays and adds to).  Waits for the context's work in flight.  IIR is bit-identical to the reference;
+ * FIR-N applies the reference's phase-shift response as a direct FIR (the same filter as its segmented FFT convolution, to
+ * rounding). */
+int oalgpu_set_tsme_encoder(oalgpu_context *ctx, int quality);
+/* ---- the bs2b crossfeed: Bs2bPostProcess (alc/alu.cpp:407-434; core/bs2b.cpp; alc/panning.cpp:1420-1433) ----
+ * The post-process of a plain stereo device with `cf_level` 1-6, the reference's headphone mode without HRTF: the dry lines
+ * are decoded to the two real lines and the Bauer stereophonic-to-binaural crossfeed filters the decoded feeds (each output
+ * is its own line high-boosted plus the other line low-passed); the direct signal already on the lines stays out of the
+ * filter.  Levels are Bs2b::*Level. */
+enum { OALGPU_BS2B_LOW = 1, OALGPU_BS2B_MIDDLE, OALGPU_BS2B_HIGH,
+       OALGPU_BS2B_LOW_EASY, OALGPU_BS2B_MIDDLE_EASY, OALGPU_BS2B_HIGH_EASY };
+/* Host only.  bs2b_processor::set_params(level, sample_rate) in the reference's own bits, out[5]: a0_lo, b1_lo, a0_hi, a1_hi,
+ * b1_hi.  OALGPU_ERR_INVALID unless 1 <= level <= 6 and sample_rate >= 1. */
+int oalgpu_crossfeed_constants(int level, uint32_t sample_rate, float out[5]);
+/* Installs the crossfeed of `level` (1-6) at the context's sample rate with fresh (zero) filter state, or removes it
+ * (level 0); off by default.  left / right: the real output lines of FrontLeft / FrontRight.  Only on a non-HRTF context
+ * that has a B-Format decoder set and no UHJ encoder, TSME encoder or front stabilizer, with left != right, both
+ * < num_real_channels: otherwise OALGPU_ERR_INVALID with nothing changed.  While it is set, oalgpu_set_bformat_decoder may
+ * replace the decoder's matrices (the filter state is kept) but refuses to remove the decoder, and the encoders' and the
+ * stabilizer's setters refuse.  It runs around the decode of every update that post-processes, on the stream that runs the
+ * post-process, before the limiter; bit-identical to the reference given the same decoded feeds.  Waits for the context's
+ * work in flight. */
+int oalgpu_set_crossfeed(oalgpu_context *ctx, int level, uint32_t left, uint32_t right);
 /* ---- the front stabilizer: StablizerPostProcess (alc/alu.cpp:329-405; core/front_stablizer.h; CreateStablizer,
  * alc/panning.cpp:160-172) ----
  * The post-process of a decoded speaker layout with a front-centre speaker when `front-stablizer` is on.  It owns the B-Format

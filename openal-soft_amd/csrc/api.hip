@@ -758,12 +758,15 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
             const DeviceLayout &D = c->L;
             // (StablizerPostProcess, alc/alu.cpp:329-405: the stabilizer owns the decode; both calls return at once without one)
             if(int rc = RunStabilizerSplit(c, c->stream, samples_to_do)) return rc;
+            if(int rc = RunCrossfeedSplit(c, c->stream, samples_to_do)) return rc;      // (Bs2bPostProcess, alc/alu.cpp:407-434: likewise)
             LaunchBFormatDecode(c->stream, c->exact, D.bus + size_t{D.numDry} * kLine, D.bus, c->decSplit.p, c->decBands.p,
                 c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, D.numDry, c->decOut, samples_to_do);
             HIP_TRY(hipGetLastError());
             if(int rc = RunStabilizer(c, c->stream, samples_to_do)) return rc;
+            if(int rc = RunCrossfeed(c, c->stream, samples_to_do)) return rc;
         }
         if(int rc = RunUhjEncoder(c, c->stream, samples_to_do)) return rc;     // (UhjPostProcess, alc/alu.cpp:300-311)
+        if(int rc = RunTsmeEncoder(c, c->stream, samples_to_do)) return rc;    // (TsmePostProcess, alc/alu.cpp:314-327)
         if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
         if(int rc = RunDistanceComp(c, c->stream, samples_to_do)) return rc;   // (ApplyDistanceComp, alc/alu.cpp:2449-2450)
         if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
@@ -928,12 +931,15 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
     if(post_process && !L.hrtf && c->decOn)
     {   // DeviceBase::Process(AmbiDecPostProcess), alc/alu.cpp:282-287: dry lines -> speaker feeds
         if(int rc = RunStabilizerSplit(c, c->postStream, samples_to_do)) return rc;      // (StablizerPostProcess: see oalgpu_post_process)
+        if(int rc = RunCrossfeedSplit(c, c->postStream, samples_to_do)) return rc;       // (Bs2bPostProcess: likewise)
         LaunchBFormatDecode(c->postStream, c->exact, L.bus + size_t{L.numDry} * kLine, L.bus, c->decSplit.p, c->decBands.p,
             c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, L.numDry, c->decOut, samples_to_do);
         HIP_TRY(hipGetLastError());
         if(int rc = RunStabilizer(c, c->postStream, samples_to_do)) return rc;
+        if(int rc = RunCrossfeed(c, c->postStream, samples_to_do)) return rc;
     }
     if(post_process && !L.hrtf) { if(int rc = RunUhjEncoder(c, c->postStream, samples_to_do)) return rc; }
+    if(post_process && !L.hrtf) { if(int rc = RunTsmeEncoder(c, c->postStream, samples_to_do)) return rc; }
     if(post_process) { if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc; }
     if(post_process && !L.hrtf) { if(int rc = RunDistanceComp(c, c->postStream, samples_to_do)) return rc; }
     if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->postStream)); c->timed = true; }

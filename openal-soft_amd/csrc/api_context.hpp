@@ -212,6 +212,16 @@ struct oalgpu_context {
     uint32_t stabLeft{0}, stabRight{0}, stabCenter{0};
     StabilizerConsts stab{};
     DevBuf<float> stabState;
+    // the stereo TSME encoder (oalgpu_set_tsme_encoder; RunTsmeEncoder, the post-process of a 4-dry / 2-real context): its quality
+    // (-1: none), FIR taps and device state
+    int tsmeQuality{-1};
+    DevBuf<float> tsmeTaps, tsmeState;
+    // the bs2b crossfeed (oalgpu_set_crossfeed; RunCrossfeedSplit / RunCrossfeed around the B-Format decode): the real lines of
+    // FrontLeft / FrontRight, its constants and device state
+    bool cfOn{false};
+    uint32_t cfLeft{0}, cfRight{0};
+    CrossfeedConsts cf{};
+    DevBuf<float> cfState;
     // speaker distance compensation (oalgpu_set_distance_comp; RunDistanceComp behind the limiter of non-HRTF contexts): per
     // output line its delay and gain, and the delay lines
     uint32_t distLines{0};
@@ -374,6 +384,9 @@ uint32_t DeviceComputeUnits(int device);
 int JoinPost(oalgpu_context *c);
 int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip
 int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
+int RunTsmeEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
+int RunCrossfeedSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip (in front of the decode)
+int RunCrossfeed(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip (behind the decode)
 int RunStabilizerSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip (in front of the decode)
 int RunStabilizer(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);  // api_output.hip (behind the decode)
 int RunDistanceComp(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip

@@ -185,9 +185,13 @@ int oalgpu_set_bformat_decoder(oalgpu_context *c, uint32_t num_out, const float 
     if(int rc = oalgpu_sync(c)) return rc;
     if((num_out == 0 || !coeffs_hf) && c->stabOn)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context's front stabilizer decodes with it (remove the stabilizer first)");
+    if((num_out == 0 || !coeffs_hf) && c->cfOn)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context's crossfeed decodes with it (remove the crossfeed first)");
     if(num_out == 0 || !coeffs_hf) { c->decOn = false; return OALGPU_OK; }
     if(c->uhjQuality >= 0)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context post-processes with its UHJ encoder");
+    if(c->tsmeQuality >= 0)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context post-processes with its TSME encoder");
     if(num_out > c->L.numReal || num_out > 32u)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: more output channels than real output lines");
     if(coeffs_lf && !(xover_norm > 0.0f && xover_norm < 0.5f))
@@ -302,6 +306,10 @@ int oalgpu_set_uhj_encoder(oalgpu_context *c, int quality)
             return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: needs three dry lines (W, X, Y) and two real output lines");
         if(c->decOn)
             return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its B-Format decoder");
+        if(c->tsmeQuality >= 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its TSME encoder");
+        if(c->cfOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its crossfeed");
     }
     // the kernels of the updates in flight are through with the old state before it goes
     if(int rc = oalgpu_sync(c)) return rc;
@@ -360,6 +368,10 @@ int oalgpu_set_front_stabilizer(oalgpu_context *c, const oalgpu_stabilizer_param
             return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: an HRTF context post-processes with MixDirectHrtf");
         if(c->uhjQuality >= 0)
             return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its UHJ encoder");
+        if(c->tsmeQuality >= 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its TSME encoder");
+        if(c->cfOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its crossfeed");
         if(!c->decOn)
             return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: needs a B-Format decoder (oalgpu_set_bformat_decoder)");
         const uint32_t nr = c->L.numReal;
@@ -401,6 +413,135 @@ int RunStabilizer(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
     const DeviceLayout &L = c->L;
     LaunchStabilizer(s, L.bus + size_t{L.numDry} * kLine, L.numReal, c->stabLeft, c->stabRight, c->stabCenter, samplesToDo, c->stab,
         c->stabState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+/* The stereo TSME encoder (TsmePostProcess, alc/alu.cpp:314-327): the quality's taps (the UHJ encoder's: the same
+ * SegmentedFilter<N>), a fresh state, and from the next update on the encode behind every post-process (RunTsmeEncoder) */
+uint32_t oalgpu_tsme_encoder_delay(int quality) { return UhjEncoderDelay(quality); }       // (TsmeEncoder*::getDelay: the same three)
+
+int oalgpu_set_tsme_encoder(oalgpu_context *c, int quality)
+{
+    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
+    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
+    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
+    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: null context");
+    if(quality >= 0)
+    {
+        if(UhjEncoderDelay(quality) == 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: not a TSME quality");
+        if(c->L.hrtf)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: an HRTF context post-processes with MixDirectHrtf");
+        if(c->L.numDry != 4 || c->L.numReal != 2)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: needs four dry lines (W, Y, Z, X) and two real output lines");
+        if(c->decOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its B-Format decoder");
+        if(c->uhjQuality >= 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its UHJ encoder");
+        if(c->stabOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its front stabilizer");
+        if(c->cfOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its crossfeed");
+    }
+    // the kernels of the updates in flight are through with the old state before it goes
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->tsmeQuality = -1;
+    if(quality >= 0)
+    {
+        if(const uint32_t len = UhjFirLength(quality))
+        {
+            const std::vector<float> taps = UhjFirTaps(len);
+            HIP_TRY(c->tsmeTaps.alloc(taps.size()));
+            HIP_TRY(c->tsmeTaps.upload(taps.data(), taps.size()));
+        }
+        const std::vector<float> init(UhjStateFloats(quality), 0.0f);
+        HIP_TRY(c->tsmeState.alloc(init.size()));
+        HIP_TRY(c->tsmeState.upload(init.data(), init.size()));
+        c->tsmeQuality = quality;
+    }
+    return OALGPU_OK;
+}
+
+// TsmeEncoder*::encode behind the update's effect slots, on the stream that runs the post-process: dry lines 0-3 (W, Y, Z, X) in,
+// the two real output lines (FrontLeft, FrontRight) delayed and added to
+int RunTsmeEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(c->tsmeQuality < 0) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    float *left = L.bus + size_t{L.numDry} * kLine;
+    LaunchTsmeEncode(s, c->tsmeQuality, left, left + kLine, L.bus, samplesToDo, c->tsmeTaps.p, c->tsmeState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+/* The bs2b crossfeed (Bs2bPostProcess, alc/alu.cpp:407-434; bs2b_processor::set_params, core/bs2b.cpp): the level's constants
+ * at the context's sample rate (host/crossfeed_params.cpp), a fresh state, and from the next update on RunCrossfeedSplit /
+ * RunCrossfeed around the decode of every post-process */
+int oalgpu_crossfeed_constants(int level, uint32_t sample_rate, float *out)
+{
+    CrossfeedConsts k{};
+    if(!out || !CrossfeedDerive(level, sample_rate, &k))
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_crossfeed_constants: needs a level of 1 to 6 and a sample rate");
+    out[0] = k.a0Lo; out[1] = k.b1Lo; out[2] = k.a0Hi; out[3] = k.a1Hi; out[4] = k.b1Hi;
+    return OALGPU_OK;
+}
+
+int oalgpu_set_crossfeed(oalgpu_context *c, int level, uint32_t left, uint32_t right)
+{
+    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
+    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
+    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
+    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: null context");
+    CrossfeedConsts k{};
+    if(level != 0)
+    {
+        if(!CrossfeedDerive(level, c->desc.sample_rate, &k))
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: not a crossfeed level (1 to 6; 0 removes)");
+        if(c->L.hrtf)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: an HRTF context post-processes with MixDirectHrtf");
+        if(c->uhjQuality >= 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: the context post-processes with its UHJ encoder");
+        if(c->tsmeQuality >= 0)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: the context post-processes with its TSME encoder");
+        if(c->stabOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: the context post-processes with its front stabilizer");
+        if(!c->decOn)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: needs a B-Format decoder (oalgpu_set_bformat_decoder)");
+        if(left >= c->L.numReal || right >= c->L.numReal || left == right)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: left and right are two different real output lines");
+    }
+    // the kernels of the updates in flight are through with the old state before it goes
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->cfOn = false;
+    if(level != 0)
+    {
+        const std::vector<float> init(kCrossfeedStateFloats, 0.0f);
+        HIP_TRY(c->cfState.alloc(init.size()));
+        HIP_TRY(c->cfState.upload(init.data(), init.size()));
+        c->cf = k;
+        c->cfLeft = left; c->cfRight = right;
+        c->cfOn = true;
+    }
+    return OALGPU_OK;
+}
+
+// in front of the decode: the direct L / R signal moves out of the filter's way (alu.cpp:416-423)
+int RunCrossfeedSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(!c->cfOn) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    LaunchCrossfeedSplit(s, L.bus + size_t{L.numDry} * kLine, c->cfLeft, c->cfRight, samplesToDo, c->cfState.p);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+// behind the decode: cross_feed over the decoded left and right lines, the direct signal added back (alu.cpp:429-433)
+int RunCrossfeed(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
+{
+    if(!c->cfOn) return OALGPU_OK;
+    const DeviceLayout &L = c->L;
+    LaunchCrossfeed(s, L.bus + size_t{L.numDry} * kLine, c->cfLeft, c->cfRight, samplesToDo, c->cf, c->cfState.p);
     HIP_TRY(hipGetLastError());
     return OALGPU_OK;
 }

@@ -10,6 +10,7 @@
 #include "../host/limiter_params.hpp"
 #include "../host/uhj_params.hpp"
 #include "../host/stabilizer_params.hpp"
+#include "../host/crossfeed_params.hpp"
 
 namespace oalgpu {
 
@@ -339,6 +340,11 @@ constexpr size_t kLimiterHoldHistory = 16u + 1024u;      // where the hold's his
 void LaunchUhjEncode(hipStream_t s, int quality, float *left, float *right, const float *w, const float *x, const float *y,
     uint32_t n, const float *taps, float *state);
 size_t UhjStateFloats(int quality);
+// ---- launcher (tsme_kernels.hip): the stereo TSME encoder of `quality` (TsmeQualityType order = kUhj*) from the four dry lines at
+// `dry` (W, Y, Z, X: ACN order) onto left / right (one workgroup); taps and state as for LaunchUhjEncode: UhjFirTaps of the
+// quality's length, UhjStateFloats(quality) floats, zero when fresh (the two encoders keep the same cascades and delay lines) ----
+void LaunchTsmeEncode(hipStream_t s, int quality, float *left, float *right, const float *dry, uint32_t n, const float *taps,
+    float *state);
 // ---- launchers (stabilizer_kernels.hip): the front stabilizer around LaunchBFormatDecode (StablizerPostProcess).  Split, in front
 // of the decode: mid = L + R and side = L - R of the real lines lidx / ridx into the state's scratch, both lines zeroed.
 // Stabilizer, behind it: the band split of the decoded mid, the all-pass of every real line, the combine (one workgroup).
@@ -352,6 +358,13 @@ void LaunchStabilizer(hipStream_t s, float *real, uint32_t numReal, uint32_t lid
 // line (device), hist: nlines x 1024 floats, zero when fresh ----
 void LaunchDistanceComp(hipStream_t s, float *lines, uint32_t nlines, uint32_t n, const uint32_t *delays, const float *gains,
     float *hist);
+// ---- launchers (crossfeed_kernels.hip): the bs2b crossfeed around LaunchBFormatDecode (Bs2bPostProcess).  Split, in front of the
+// decode: the real lines lidx / ridx move into the state's scratch, both lines zeroed.  Crossfeed, behind it: cross_feed over the
+// two decoded lines, then + the saved direct lines (one workgroup).  state: kCrossfeedStateFloats floats, zero when fresh ----
+constexpr size_t kCrossfeedScratch = 64;                        // where the direct left[1024] | right[1024] start in the state
+constexpr size_t kCrossfeedStateFloats = kCrossfeedScratch + 2 * kLine;
+void LaunchCrossfeedSplit(hipStream_t s, float *real, uint32_t lidx, uint32_t ridx, uint32_t n, float *state);
+void LaunchCrossfeed(hipStream_t s, float *real, uint32_t lidx, uint32_t ridx, uint32_t n, const CrossfeedConsts &k, float *state);
 // ---- launcher (effects_kernels.hip): equalizer / modulator / echo / dedicated, one workgroup per instance ----
 constexpr uint32_t kFxMaxIn = 16;
 struct FxState {                       // device-resident per instance

@@ -1,141 +1,39 @@
 // The stereo UHJ encoder: UhjPostProcess (alc/alu.cpp:300-311) over the dry lines W, X, Y and the two real output lines,
-// one workgroup of four wavefronts per context and update.
-//
-// IIR (UhjEncoderIIR::encode, core/uhjfilter.cpp).  Each all-pass section of allpass_iir.hpp computes
-// y_n = c x_n + z0 with z0 = c y_{n-2} - x_{n-2}: even and odd samples form independent chains through all four sections.
-// The five cascades (S, the W/X mix of D, Y, the two direct lines) x two parities are ten serial chains, one lane each on
-// wavefront 0, their inputs and outputs staged in LDS; the input mixes, the one-sample delays and the final combine run
-// 256 samples wide.  The reference's float operations in its order (mul then add, (S + D) + direct): bit-identical.
-//
-// FIR-N (UhjEncoder<N>::encode).  The reference's segmented FFT convolution is the linear FIR
-// jwx[t] = sum_i h[2i+1] wx[t - 128 - (2i+1)] (host/uhj_params.cpp); here a direct sum over the N/2 nonzero taps, one sample
-// per thread, accumulated in double.  S, 0.267586995182 Y and the direct lines are delayed by N/2 + 128.  Histories live in
-// the context's state buffer and are staged in LDS with the update's samples behind them.
-#include "kernels.hpp"
+// one workgroup of four wavefronts per context and update.  The IIR and FIR-N forms are those of dev_encoder.hpp with
+// UhjEncoderIIR's / UhjEncoder<N>'s input mixes (core/uhjfilter.cpp) and Y's gain 0.267586995182 in D.
+#include "dev_encoder.hpp"
 
 #pragma clang fp contract(off)
 
 namespace oalgpu {
 namespace {
 
-constexpr uint32_t kUhjThreads = 256;
-constexpr float kF1[4] = {0.479400865589f, 0.876218493539f, 0.976597589508f, 0.997499255936f};   // Filter1Coeff
-constexpr float kF2[4] = {0.161758498368f, 0.733028932341f, 0.945349700329f, 0.990599156684f};   // Filter2Coeff
+constexpr uint32_t kUhjThreads = kEncThreads;
+constexpr float kUhjYGain = 0.267586995182f;
 
-// state (UhjStateFloats(IIR)): [cascade][section][z0, z1] for the cascades S, WX, Y, L, R (40 floats) | the carried samples
-// mDelayWX, mDelayY, mDirectDelay[0], mDirectDelay[1]
+// S = 0.4698463 W + 0.0757602682546 X; the W/X part of D = j(-0.17101005 W + 0.208149636675 X)
+struct UhjMix {
+    const float *w, *x, *y;
+    __device__ __forceinline__ void operator()(uint32_t i, float &s, float &wx, float &yv) const
+    {
+        const float wv = w[i], xv = x[i];
+        s = 0.4698463f * wv + 0.0757602682546f * xv;
+        wx = -0.17101005f * wv + 0.208149636675f * xv;
+        yv = y[i];
+    }
+};
+
 __global__ __launch_bounds__(kUhjThreads) void UhjIirKernel(float *left, float *right, const float *w, const float *x,
     const float *y, uint32_t n, float *state)
 {
-    __shared__ float buf[5][kLine];            // the cascades' inputs, overwritten by their outputs
-    const uint32_t t = threadIdx.x;
-    for(uint32_t i = t; i < n; i += kUhjThreads)
-    {
-        const float wv = w[i], xv = x[i];
-        buf[0][i] = 0.4698463f * wv + 0.0757602682546f * xv;
-        buf[1][i] = -0.17101005f * wv + 0.208149636675f * xv;
-        buf[2][i] = y[i];
-        buf[3][i] = left[i];
-        buf[4][i] = right[i];
-    }
-    __syncthreads();
-    if(t < 10u)
-    {
-        const uint32_t casc = t >> 1, par = t & 1u;
-        float c[4], s[4];
-#pragma unroll
-        for(int k = 0; k < 4; ++k)
-        {
-            c[k] = casc == 1u ? kF2[k] : kF1[k];
-            s[k] = state[casc * 8u + uint32_t(k) * 2u + par];
-        }
-        float *line = buf[casc];
-#pragma unroll 4
-        for(uint32_t i = par; i < n; i += 2u)
-        {
-            float v = line[i];
-#pragma unroll
-            for(int k = 0; k < 4; ++k)
-            {
-                const float yk = v * c[k] + s[k];
-                s[k] = yk * c[k] - v;
-                v = yk;
-            }
-            line[i] = v;
-        }
-        // z0 takes the chain of the update's second-to-last sample, z1 the last's (for n = 1 the odd chain's
-        // value moves to z0 untouched)
-        const uint32_t slot = (n & 1u) ? (par ^ 1u) : par;
-#pragma unroll
-        for(int k = 0; k < 4; ++k) state[casc * 8u + uint32_t(k) * 2u + slot] = s[k];
-    }
-    __syncthreads();
-    float *carry = state + 40;
-    for(uint32_t i = t; i < n; i += kUhjThreads)
-    {
-        // S and Y, and the direct lines, through the one-sample delay
-        const float sv = i ? buf[0][i - 1] : carry[0];
-        const float yv = i ? buf[2][i - 1] : carry[1];
-        const float lv = i ? buf[3][i - 1] : carry[2];
-        const float rv = i ? buf[4][i - 1] : carry[3];
-        const float dv = buf[1][i] + 0.267586995182f * yv;
-        left[i] = sv + dv + lv;
-        right[i] = sv - dv + rv;
-    }
-    __syncthreads();                           // (thread 0 read the old carried samples above)
-    if(t == 0)
-    {
-        carry[0] = buf[0][n - 1]; carry[1] = buf[2][n - 1];
-        carry[2] = buf[3][n - 1]; carry[3] = buf[4][n - 1];
-    }
+    EncodeIir(left, right, n, state, kUhjYGain, UhjMix{w, x, y});
 }
 
-// state (UhjStateFloats(FIR-N)): the W/X mix's history (N + 127) | the last d samples of S, Y, left, right (d = N/2 + 128)
 template<uint32_t N>
 __global__ __launch_bounds__(kUhjThreads) void UhjFirKernel(float *left, float *right, const float *w, const float *x,
     const float *y, uint32_t n, const float *taps, float *state)
 {
-    constexpr uint32_t kH = N + 127u, kD = N / 2u + 128u;
-    __shared__ float wx[kH + kLine];
-    __shared__ float dl[4][kD + kLine];        // [history | this update's] of S, Y, left, right
-    const uint32_t t = threadIdx.x;
-    float *hist = state;
-    float *dhist = state + kH;
-    for(uint32_t j = t; j < kH; j += kUhjThreads) wx[j] = hist[j];
-    for(uint32_t j = t; j < kD; j += kUhjThreads)
-    {
-#pragma unroll
-        for(int q = 0; q < 4; ++q) dl[q][j] = dhist[q * kD + j];
-    }
-    for(uint32_t i = t; i < n; i += kUhjThreads)
-    {
-        const float wv = w[i], xv = x[i];
-        wx[kH + i] = -0.17101005f * wv + 0.208149636675f * xv;
-        dl[0][kD + i] = 0.4698463f * wv + 0.0757602682546f * xv;
-        dl[1][kD + i] = y[i];
-        dl[2][kD + i] = left[i];
-        dl[3][kD + i] = right[i];
-    }
-    __syncthreads();
-    for(uint32_t i = t; i < n; i += kUhjThreads)
-    {
-        // jwx[i] = sum_k taps[k] * wx[i - 129 - 2k]: ext index kH + i - 129 - 2k >= 0 for k < N/2
-        const float *src = wx + (kH + i - 129u);
-        double acc = 0.0;
-#pragma unroll 8
-        for(uint32_t k = 0; k < N / 2u; ++k) acc = fma(double(taps[k]), double(src[-int(2u * k)]), acc);
-        const float jwx = float(acc);
-        const float sv = dl[0][i], dv = jwx + 0.267586995182f * dl[1][i];
-        left[i] = dl[2][i] + (sv + dv);
-        right[i] = dl[3][i] + (sv - dv);
-    }
-    // the next update's histories: the last kH / kD samples of [history | update]
-    for(uint32_t j = t; j < kH; j += kUhjThreads) hist[j] = wx[n + j];
-    for(uint32_t j = t; j < kD; j += kUhjThreads)
-    {
-#pragma unroll
-        for(int q = 0; q < 4; ++q) dhist[q * kD + j] = dl[q][n + j];
-    }
+    EncodeFir<N>(left, right, n, taps, state, kUhjYGain, UhjMix{w, x, y});
 }
 
 } // namespace
@@ -153,9 +51,8 @@ void LaunchUhjEncode(hipStream_t s, int quality, float *left, float *right, cons
 
 size_t UhjStateFloats(int quality)
 {
-    if(quality == kUhjIir) return 44u;
-    const uint32_t len = UhjFirLength(quality);
-    return size_t{len + 127u} + 4u * size_t{UhjEncoderDelay(quality)};
+    if(quality == kUhjIir) return kEncIirStateFloats;
+    return EncFirStateFloats(UhjFirLength(quality));
 }
 
 } // namespace oalgpu

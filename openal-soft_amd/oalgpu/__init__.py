@@ -237,6 +237,27 @@ def uhj_encoder_delay(quality):
     return int(lib.oalgpu_uhj_encoder_delay(quality))
 
 
+(TSME_IIR, TSME_FIR256, TSME_FIR512) = range(3)              # enum oalgpu_tsme_quality (TsmeQualityType order)
+
+
+def tsme_encoder_delay(quality):
+    """The TSME encoder's delay in samples (getDelay): 1, 256 or 384; 0 for an invalid quality."""
+    lib.oalgpu_tsme_encoder_delay.argtypes = [C.c_int]
+    lib.oalgpu_tsme_encoder_delay.restype = C.c_uint32
+    return int(lib.oalgpu_tsme_encoder_delay(quality))
+
+
+(BS2B_LOW, BS2B_MIDDLE, BS2B_HIGH, BS2B_LOW_EASY, BS2B_MIDDLE_EASY, BS2B_HIGH_EASY) = range(1, 7)   # Bs2b::*Level
+
+
+def crossfeed_constants(level, rate):
+    """bs2b_processor::set_params(level, rate) as float32[5]: a0_lo, b1_lo, a0_hi, a1_hi, b1_hi."""
+    out = np.zeros(5, np.float32)
+    lib.oalgpu_crossfeed_constants.argtypes = [C.c_int, C.c_uint32, f32p]
+    check(lib.oalgpu_crossfeed_constants(level, rate, _fp(out)), "oalgpu_crossfeed_constants")
+    return out
+
+
 class StabilizerParams(C.Structure):
     """oalgpu_stabilizer_params"""
     _fields_ = [("left", C.c_uint32), ("right", C.c_uint32), ("center", C.c_uint32), ("xover_norm", C.c_float)]
@@ -725,6 +746,17 @@ class Scene:
         """Installs a fresh stereo UHJ encoder (UHJ_IIR, UHJ_FIR256, UHJ_FIR512) as the post-process, or removes it (None)."""
         lib.oalgpu_set_uhj_encoder.argtypes = [C.c_void_p, C.c_int]
         check(lib.oalgpu_set_uhj_encoder(self.h, -1 if quality is None else quality), "oalgpu_set_uhj_encoder")
+
+    def set_tsme_encoder(self, quality):
+        """Installs a fresh stereo TSME encoder (TSME_IIR, TSME_FIR256, TSME_FIR512) as the post-process, or removes it (None)."""
+        lib.oalgpu_set_tsme_encoder.argtypes = [C.c_void_p, C.c_int]
+        check(lib.oalgpu_set_tsme_encoder(self.h, -1 if quality is None else quality), "oalgpu_set_tsme_encoder")
+
+    def set_crossfeed(self, level, left=0, right=1):
+        """Installs a fresh bs2b crossfeed (BS2B_*: 1-6) around the B-Format decode (left / right: the real output lines of
+        FrontLeft / FrontRight), or removes it (None)."""
+        lib.oalgpu_set_crossfeed.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]
+        check(lib.oalgpu_set_crossfeed(self.h, 0 if level is None else level, left, right), "oalgpu_set_crossfeed")
 
     def set_front_stabilizer(self, left, right=None, center=None, xover_norm=5000.0 / 48000.0):
         """Installs a fresh front stabilizer around the B-Format decode (left / right / center: the real output lines of
