@@ -2,7 +2,7 @@
 // HBM allocation/upload, parameter preparation that the reference does with libm on its mixer
 // thread (resampler state, biquad design), and kernel launches on the context's stream.
 // No CPU fallback exists anywhere in this file: without a HIP device every entry point fails.
-// (The rest of the C-ABI: api_comm.hip, api_percall.hip, api_hrtf.hip, api_voices.hip, api_output.hip, api_callback.hip; shared: api_context.hpp.)
+// (The rest of the C-ABI: api_comm.hip, api_percall.hip, api_hrtf.hip, api_voices.hip, api_output.hip, api_poststage.hip, api_callback.hip; shared: api_context.hpp.)
 #include "api_context.hpp"
 namespace oalgpu {
 
@@ -752,23 +752,8 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
     if(int rc = JoinPost(c)) return rc;
     if(int rc = RunEffects(c, c->stream, samples_to_do)) return rc;
     if(!c->L.hrtf)
-    {   // DeviceBase::Process(AmbiDecPostProcess), alc/alu.cpp:282-287: dry lines -> speaker feeds
-        if(c->decOn)
-        {
-            const DeviceLayout &D = c->L;
-            // (StablizerPostProcess, alc/alu.cpp:329-405: the stabilizer owns the decode; both calls return at once without one)
-            if(int rc = RunStabilizerSplit(c, c->stream, samples_to_do)) return rc;
-            if(int rc = RunCrossfeedSplit(c, c->stream, samples_to_do)) return rc;      // (Bs2bPostProcess, alc/alu.cpp:407-434: likewise)
-            LaunchBFormatDecode(c->stream, c->exact, D.bus + size_t{D.numDry} * kLine, D.bus, c->decSplit.p, c->decBands.p,
-                c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, D.numDry, c->decOut, samples_to_do);
-            HIP_TRY(hipGetLastError());
-            if(int rc = RunStabilizer(c, c->stream, samples_to_do)) return rc;
-            if(int rc = RunCrossfeed(c, c->stream, samples_to_do)) return rc;
-        }
-        if(int rc = RunUhjEncoder(c, c->stream, samples_to_do)) return rc;     // (UhjPostProcess, alc/alu.cpp:300-311)
-        if(int rc = RunTsmeEncoder(c, c->stream, samples_to_do)) return rc;    // (TsmePostProcess, alc/alu.cpp:314-327)
-        if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
-        if(int rc = RunDistanceComp(c, c->stream, samples_to_do)) return rc;   // (ApplyDistanceComp, alc/alu.cpp:2449-2450)
+    {
+        if(int rc = RunSpeakerPost(c, c->stream, samples_to_do)) return rc;
         if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
         return OALGPU_OK;
     }
@@ -811,6 +796,13 @@ int oalgpu_mix_update(oalgpu_context *c, uint32_t samples_to_do, int post_proces
         return OALGPU_OK;
     }
     return RunMixUpdate(c, samples_to_do, post_process, nullptr);
+}
+
+int BeginSetter(oalgpu_context *c, const char *who)
+{
+    if(!c) return Fail(OALGPU_ERR_INVALID, std::string(who) + ": null context");
+    if(int rc = FlushPendingMix(c)) return rc;
+    return c->res.pendingBlock ? UseCtx(c) : OALGPU_OK;
 }
 
 int FlushPendingMix(oalgpu_context *c, oalgpu_param_block *next)
@@ -926,22 +918,13 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
         c->lastPostEvent = (ev && !c->limOn) ? ev : c->evPostDone;
         if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, ev)) return rc;
         postDoneBound = ev != nullptr && !c->limOn;
+        if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc;
     }
-    else c->lastPostEvent = c->evPostDone;
-    if(post_process && !L.hrtf && c->decOn)
-    {   // DeviceBase::Process(AmbiDecPostProcess), alc/alu.cpp:282-287: dry lines -> speaker feeds
-        if(int rc = RunStabilizerSplit(c, c->postStream, samples_to_do)) return rc;      // (StablizerPostProcess: see oalgpu_post_process)
-        if(int rc = RunCrossfeedSplit(c, c->postStream, samples_to_do)) return rc;       // (Bs2bPostProcess: likewise)
-        LaunchBFormatDecode(c->postStream, c->exact, L.bus + size_t{L.numDry} * kLine, L.bus, c->decSplit.p, c->decBands.p,
-            c->decGainsHf.p, c->decDual ? c->decGainsLf.p : nullptr, L.numDry, c->decOut, samples_to_do);
-        HIP_TRY(hipGetLastError());
-        if(int rc = RunStabilizer(c, c->postStream, samples_to_do)) return rc;
-        if(int rc = RunCrossfeed(c, c->postStream, samples_to_do)) return rc;
+    else
+    {
+        c->lastPostEvent = c->evPostDone;
+        if(post_process) { if(int rc = RunSpeakerPost(c, c->postStream, samples_to_do)) return rc; }
     }
-    if(post_process && !L.hrtf) { if(int rc = RunUhjEncoder(c, c->postStream, samples_to_do)) return rc; }
-    if(post_process && !L.hrtf) { if(int rc = RunTsmeEncoder(c, c->postStream, samples_to_do)) return rc; }
-    if(post_process) { if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc; }
-    if(post_process && !L.hrtf) { if(int rc = RunDistanceComp(c, c->postStream, samples_to_do)) return rc; }
     if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->postStream)); c->timed = true; }
     if(!postDoneBound) HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));
     c->postPending = true;
@@ -963,10 +946,7 @@ int oalgpu_sync(oalgpu_context *c)
 
 int oalgpu_set_timing(oalgpu_context *c, int enable)
 {
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
+    if(int rc = BeginSetter(c, "oalgpu_set_timing")) return rc;
     c->timing = enable != 0;
     c->timed = false;
     return OALGPU_OK;
@@ -1172,10 +1152,7 @@ int oalgpu_resident_set_max_updates(oalgpu_context *c, uint32_t max_updates)
 
 int oalgpu_set_carry_accum(oalgpu_context *c, int enable)
 {
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
+    if(int rc = BeginSetter(c, "oalgpu_set_carry_accum")) return rc;
     c->carryAccum = enable != 0;
     return OALGPU_OK;
 }

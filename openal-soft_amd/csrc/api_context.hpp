@@ -1,6 +1,7 @@
 // The device context and what the C-ABI translation units share (api.hip: context life, the update, slots; api_comm.hip: the
 // sharded update's transports; api_percall.hip: the per-call operators; api_hrtf.hip: HRTF data sets; api_voices.hip: buffers, voices,
-// parameters; api_output.hip: what comes back; api_callback.hip: callback sources).  Host logic only; no CPU fallback anywhere.
+// parameters; api_output.hip: what comes back; api_poststage.hip: what is installed and run behind the buses; api_callback.hip:
+// callback sources).  Host logic only; no CPU fallback anywhere.
 #pragma once
 #include "../../include/oalgpu.h"
 #ifdef OALGPU_MEASUREMENT
@@ -76,6 +77,10 @@ struct TableBlob {
 inline const TableBlob &Blob() { static const TableBlob b; return b; }
 
 } // namespace oalgpu
+
+// The post-process of a non-HRTF context: the reference keeps ONE PostProcess variant per device (core/device.h) and so does the
+// context.  Stabilizer and Bs2b decode with the B-Format decoder installed under them; HRTF contexts are DeviceLayout::hrtf.
+enum class PostKind : uint32_t { None, AmbiDec, Stabilizer, Bs2b, Uhj, Tsme };
 
 struct BusTransport;
 struct oalgpu_context {
@@ -190,39 +195,35 @@ struct oalgpu_context {
     // right behind the partial-bus reduction, on the stream that runs it
     struct BusTransport *comm{nullptr};
     int commRank{0}, commWorld{1};
-    // the stage behind the buses (output_kernels.hip): AmbiDecPostProcess of non-HRTF contexts, dither, PCM
-    bool decOn{false}, decDual{false};
+    // the stage behind the buses (api_poststage.hip): the one post-process of a non-HRTF context and what each kind keeps
+    PostKind post{PostKind::None};
+    // the B-Format decoder (oalgpu_set_bformat_decoder: AmbiDec, and under Stabilizer and Bs2b)
+    bool decDual{false};
     uint32_t decOut{0};
     DevBuf<float> decGainsHf, decGainsLf, decBands;
     DevBuf<SplitterState> decSplit;
+    // the output format (oalgpu_set_output; oalgpu_read_output: dither, PCM)
     int outType{6};                        // DevFmtType order: 0 i8, 1 u8, 2 i16, 3 u16, 4 i32, 5 u32, 6 f32
     float ditherDepth{0.0f};
     uint32_t ditherSeed{22222};
-    // the output limiter (oalgpu_set_output_limiter; RunLimiter behind every post-process): its constants and device state
+    // the output limiter (oalgpu_set_output_limiter; RunLimiter behind every post-process, HRTF included): its constants and device state
     bool limOn{false};
     LimiterConsts lim{};
     DevBuf<float> limState;
-    // the stereo UHJ encoder (oalgpu_set_uhj_encoder; RunUhjEncoder, the post-process of a 3-dry / 2-real context): its quality
-    // (-1: none), FIR taps and device state
-    int uhjQuality{-1};
-    DevBuf<float> uhjTaps, uhjState;
-    // the front stabilizer (oalgpu_set_front_stabilizer; RunStabilizerSplit / RunStabilizer around the B-Format decode): the real
-    // lines of FrontLeft / FrontRight / FrontCenter, its constants and device state
-    bool stabOn{false};
+    // the stereo encoder (oalgpu_set_uhj_encoder: Uhj, 3 dry / 2 real lines; oalgpu_set_tsme_encoder: Tsme, 4 dry / 2 real
+    // lines): its quality, FIR taps and device state
+    int encQuality{-1};
+    DevBuf<float> encTaps, encState;
+    // the front stabilizer (oalgpu_set_front_stabilizer: Stabilizer): the real lines of FrontLeft / FrontRight / FrontCenter,
+    // its constants and device state
     uint32_t stabLeft{0}, stabRight{0}, stabCenter{0};
     StabilizerConsts stab{};
     DevBuf<float> stabState;
-    // the stereo TSME encoder (oalgpu_set_tsme_encoder; RunTsmeEncoder, the post-process of a 4-dry / 2-real context): its quality
-    // (-1: none), FIR taps and device state
-    int tsmeQuality{-1};
-    DevBuf<float> tsmeTaps, tsmeState;
-    // the bs2b crossfeed (oalgpu_set_crossfeed; RunCrossfeedSplit / RunCrossfeed around the B-Format decode): the real lines of
-    // FrontLeft / FrontRight, its constants and device state
-    bool cfOn{false};
+    // the bs2b crossfeed (oalgpu_set_crossfeed: Bs2b): the real lines of FrontLeft / FrontRight, its constants and device state
     uint32_t cfLeft{0}, cfRight{0};
     CrossfeedConsts cf{};
     DevBuf<float> cfState;
-    // speaker distance compensation (oalgpu_set_distance_comp; RunDistanceComp behind the limiter of non-HRTF contexts): per
+    // speaker distance compensation (oalgpu_set_distance_comp; behind the limiter of non-HRTF contexts): per
     // output line its delay and gain, and the delay lines
     uint32_t distLines{0};
     DevBuf<uint32_t> distDelays;
@@ -382,14 +383,15 @@ int FlushInits(oalgpu_context *c);
 int AllocStreamRows(oalgpu_context *c);
 uint32_t DeviceComputeUnits(int device);
 int JoinPost(oalgpu_context *c);
-int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip
-int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
-int RunTsmeEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
-int RunCrossfeedSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip (in front of the decode)
-int RunCrossfeed(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_output.hip (behind the decode)
-int RunStabilizerSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip (in front of the decode)
-int RunStabilizer(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);  // api_output.hip (behind the decode)
-int RunDistanceComp(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo); // api_output.hip
+// what every setter that may follow a deferred update starts with: the update is submitted, a parameter block that waits for a
+// resident update goes in (it was applied BEFORE this call, as on the launched path), and a null context is `who`'s error
+int BeginSetter(oalgpu_context *c, const char *who);
+int RunSpeakerPost(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);   // api_poststage.hip (a non-HRTF update's whole post stage)
+int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo);       // api_poststage.hip (behind an HRTF post-process)
+bool RingEligible(const oalgpu_context *c);                        // api_output.hip
+// RealOut: the real output lines, or the dry lines themselves where the device has none (core/device.h:300)
+inline float *RealOut(const oalgpu_context *c) { return c->L.numReal ? c->L.bus + size_t{c->L.numDry} * kLine : c->L.bus; }
+inline uint32_t RealOutLines(const oalgpu_context *c) { return c->L.numReal ? c->L.numReal : c->L.numDry; }
 bool HostStoresReachDevice(oalgpu_context *c);                     // api_voices.hip
 int AllocBufferHandle(oalgpu_context *c, uint32_t *out);           // api_voices.hip
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip

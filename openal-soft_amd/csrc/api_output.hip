@@ -1,14 +1,12 @@
-// What comes back: the output ring, voice-event reports, the caller's stream, bus and voice read-backs.
+// What comes back: the output ring, voice-event reports, the caller's stream, the output format and its PCM, bus and voice
+// read-backs.  (What is installed behind the buses and run per update: api_poststage.hip.)
 #include "api_context.hpp"
 
-static size_t OutputLineFloats(const oalgpu_context *c)
-{
-    return size_t{c->L.numReal ? c->L.numReal : c->L.numDry} * kLine;
-}
+static size_t OutputLineFloats(const oalgpu_context *c) { return size_t{RealOutLines(c)} * kLine; }
 
 // The post-process kernel stores the output ring's slots itself where it writes the context's last word on the lines: an HRTF
 // context's fused FAST post-process with its two output lines, and no limiter behind it (with one, the slots take the copy).
-static bool RingEligible(const oalgpu_context *c)
+bool RingEligible(const oalgpu_context *c)
 {
     return c->L.hrtf && c->L.numReal == 2 && c->useWave && OutputLineFloats(c) == size_t{2} * kLine && !c->limOn;
 }
@@ -51,8 +49,7 @@ int oalgpu_read_output_async(oalgpu_context *c, uint32_t *ticket)
     c->outUpdate[slot] = c->updatesSubmitted;
     // behind whatever produced the lines: the post stream of a pipelined context, else the main one
     hipStream_t s = (c->useWave && c->ownStream && !c->serialOnly && c->postStream) ? c->postStream : c->stream;
-    const float *src = c->L.numReal ? c->L.bus + size_t{c->L.numDry} * kLine : c->L.bus;
-    HIP_TRY(hipMemcpyAsync(c->outHost[slot], src, floats * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c->outHost[slot], RealOut(c), floats * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(c->outDone[slot], s));
     // (a resident context's next reduction runs on a stream of its own and rewrites these lines: it has to wait for the copy)
     if(c->res.running) c->res.copyPending = c->outDone[slot];
@@ -175,425 +172,13 @@ int oalgpu_read_dry(oalgpu_context *c, float *out)
     return OALGPU_OK;
 }
 
-/* BFormatDec(inchans = num_dry_channels, coeffs, coeffslf, xover_f0norm), core/bformatdec.cpp:27-58 */
-int oalgpu_set_bformat_decoder(oalgpu_context *c, uint32_t num_out, const float *coeffs_hf, const float *coeffs_lf,
-    float xover_norm)
-{
-    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
-    if(c->L.hrtf) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: an HRTF context post-processes with MixDirectHrtf");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = oalgpu_sync(c)) return rc;
-    if((num_out == 0 || !coeffs_hf) && c->stabOn)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context's front stabilizer decodes with it (remove the stabilizer first)");
-    if((num_out == 0 || !coeffs_hf) && c->cfOn)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context's crossfeed decodes with it (remove the crossfeed first)");
-    if(num_out == 0 || !coeffs_hf) { c->decOn = false; return OALGPU_OK; }
-    if(c->uhjQuality >= 0)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context post-processes with its UHJ encoder");
-    if(c->tsmeQuality >= 0)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: the context post-processes with its TSME encoder");
-    if(num_out > c->L.numReal || num_out > 32u)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: more output channels than real output lines");
-    if(coeffs_lf && !(xover_norm > 0.0f && xover_norm < 0.5f))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_bformat_decoder: a dual-band decoder needs 0 < xover_norm < 0.5");
-    const uint32_t nin = c->L.numDry;
-    // decoder[j].mGains[out] = coeffs[out][j] (bformatdec.cpp:33-38): stored [dry line][32]
-    std::vector<float> hf(size_t{nin} * 32, 0.0f), lf(size_t{nin} * 32, 0.0f);
-    for(uint32_t j = 0; j < nin && j < OALGPU_MAX_AMBI_CHANNELS; ++j)
-        for(uint32_t o = 0; o < num_out; ++o)
-        {
-            hf[j * 32 + o] = coeffs_hf[size_t{o} * OALGPU_MAX_AMBI_CHANNELS + j];
-            if(coeffs_lf) lf[j * 32 + o] = coeffs_lf[size_t{o} * OALGPU_MAX_AMBI_CHANNELS + j];
-        }
-    HIP_TRY(c->decGainsHf.alloc(hf.size())); HIP_TRY(c->decGainsHf.upload(hf.data(), hf.size()));
-    HIP_TRY(c->decGainsLf.alloc(lf.size())); HIP_TRY(c->decGainsLf.upload(lf.data(), lf.size()));
-    HIP_TRY(c->decBands.alloc(size_t{nin} * 2 * kLine)); HIP_TRY(c->decBands.zero());
-    std::vector<SplitterState> sp(nin);
-    for(auto &s : sp) s = SplitterState{coeffs_lf ? SplitterCoeff(xover_norm) : 0.0f, 0.0f, 0.0f, 0.0f};
-    HIP_TRY(c->decSplit.alloc(nin)); HIP_TRY(c->decSplit.upload(sp.data(), nin));
-    c->decOut = num_out; c->decDual = coeffs_lf != nullptr; c->decOn = true;
-    return OALGPU_OK;
-}
-
 /* the device's output format: DevFmtType (core/devformat.h:56-64), DitherDepth / DitherSeed (alc/alc.cpp) */
 int oalgpu_set_output(oalgpu_context *c, int sample_type, float dither_depth, uint32_t dither_seed)
 {
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c || sample_type < OALGPU_OUT_I8 || sample_type > OALGPU_OUT_F32 || dither_depth < 0.0f)
+    if(int rc = BeginSetter(c, "oalgpu_set_output")) return rc;
+    if(sample_type < OALGPU_OUT_I8 || sample_type > OALGPU_OUT_F32 || dither_depth < 0.0f)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output: bad arguments");
     c->outType = sample_type; c->ditherDepth = dither_depth; c->ditherSeed = dither_seed;
-    return OALGPU_OK;
-}
-
-/* The device's output limiter: Compressor::Create's constants (host/limiter_params.cpp), a fresh state, and from the next update
- * on Compressor::process behind every post-process (RunLimiter) */
-int oalgpu_limiter_device_params(uint32_t sample_rate, int sample_type, float dither_depth, oalgpu_limiter_params *out)
-{
-    if(!out || sample_rate == 0 || sample_type < OALGPU_OUT_I8 || sample_type > OALGPU_OUT_F32 || !(dither_depth >= 0.0f))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_limiter_device_params: bad arguments");
-    return LimiterDeviceParams(sample_rate, sample_type, dither_depth, out) ? 1 : 0;
-}
-
-uint32_t oalgpu_limiter_look_ahead(const oalgpu_limiter_params *params)
-{
-    LimiterConsts k{};
-    if(!params || !LimiterDerive(*params, &k)) return 0u;
-    return k.lookAhead;
-}
-
-int oalgpu_set_output_limiter(oalgpu_context *c, const oalgpu_limiter_params *params)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output_limiter: null context");
-    const uint32_t nlines = c->L.numReal ? c->L.numReal : c->L.numDry;
-    LimiterConsts k{};
-    if(params)
-    {
-        if(params->num_channels != 0 && params->num_channels != nlines)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output_limiter: num_channels is not the context's number of output lines");
-        if(!LimiterDerive(*params, &k))
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output_limiter: bad parameters");
-        k.numChans = nlines;
-    }
-    // the kernels of the updates in flight are through with the old state before it goes
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->limOn = false;
-    if(params)
-    {
-        std::vector<float> init(LimiterStateFloats(nlines), 0.0f);
-        std::fill(init.begin() + kLimiterHoldHistory, init.begin() + kLimiterHoldHistory + kLine, -INFINITY);
-        HIP_TRY(c->limState.alloc(init.size()));
-        HIP_TRY(c->limState.upload(init.data(), init.size()));
-        c->lim = k;
-        c->limOn = true;
-    }
-    if(c->outFloats) c->outRing = RingEligible(c);
-    return OALGPU_OK;
-}
-
-// Compressor::process behind the update's post-process, on the stream that ran it (alc/alu.cpp:2446): RealOut is the real
-// output lines, or the dry lines themselves where the context has none
-int RunLimiter(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(!c->limOn) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    LaunchLimiter(s, L.numReal ? L.bus + size_t{L.numDry} * kLine : L.bus, samplesToDo, c->lim, c->limState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-/* The stereo UHJ encoder (UhjPostProcess, alc/alu.cpp:300-311): the quality's taps (host/uhj_params.cpp), a fresh state, and
- * from the next update on the encode behind every post-process (RunUhjEncoder) */
-uint32_t oalgpu_uhj_encoder_delay(int quality) { return UhjEncoderDelay(quality); }
-
-int oalgpu_set_uhj_encoder(oalgpu_context *c, int quality)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: null context");
-    if(quality >= 0)
-    {
-        if(UhjEncoderDelay(quality) == 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: not a UHJ quality");
-        if(c->L.hrtf)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: an HRTF context post-processes with MixDirectHrtf");
-        if(c->L.numDry != 3 || c->L.numReal != 2)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: needs three dry lines (W, X, Y) and two real output lines");
-        if(c->decOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its B-Format decoder");
-        if(c->tsmeQuality >= 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its TSME encoder");
-        if(c->cfOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_uhj_encoder: the context post-processes with its crossfeed");
-    }
-    // the kernels of the updates in flight are through with the old state before it goes
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->uhjQuality = -1;
-    if(quality >= 0)
-    {
-        if(const uint32_t len = UhjFirLength(quality))
-        {
-            const std::vector<float> taps = UhjFirTaps(len);
-            HIP_TRY(c->uhjTaps.alloc(taps.size()));
-            HIP_TRY(c->uhjTaps.upload(taps.data(), taps.size()));
-        }
-        const std::vector<float> init(UhjStateFloats(quality), 0.0f);
-        HIP_TRY(c->uhjState.alloc(init.size()));
-        HIP_TRY(c->uhjState.upload(init.data(), init.size()));
-        c->uhjQuality = quality;
-    }
-    return OALGPU_OK;
-}
-
-// UhjEncoder*::encode behind the update's effect slots, on the stream that runs the post-process: dry lines 0-2 (W, X, Y) in,
-// the two real output lines (FrontLeft, FrontRight) delayed and added to
-int RunUhjEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(c->uhjQuality < 0) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    float *left = L.bus + size_t{L.numDry} * kLine;
-    LaunchUhjEncode(s, c->uhjQuality, left, left + kLine, L.bus, L.bus + kLine, L.bus + 2 * kLine, samplesToDo, c->uhjTaps.p,
-        c->uhjState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-/* The front stabilizer (StablizerPostProcess, alc/alu.cpp:329-405; CreateStablizer, alc/panning.cpp:160-172): the constants
- * (host/stabilizer_params.cpp), a fresh state, and from the next update on RunStabilizerSplit / RunStabilizer around the decode
- * of every post-process */
-int oalgpu_front_stabilizer_constants(float xover_norm, float *out)
-{
-    StabilizerConsts k{};
-    if(!out || !StabilizerDerive(xover_norm, &k))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_front_stabilizer_constants: needs 0 < xover_norm < 0.5");
-    out[0] = k.coeff; out[1] = k.midLf; out[2] = k.midHf; out[3] = k.centerLf; out[4] = k.centerHf;
-    return OALGPU_OK;
-}
-
-int oalgpu_set_front_stabilizer(oalgpu_context *c, const oalgpu_stabilizer_params *params)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: null context");
-    StabilizerConsts k{};
-    if(params)
-    {
-        if(c->L.hrtf)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: an HRTF context post-processes with MixDirectHrtf");
-        if(c->uhjQuality >= 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its UHJ encoder");
-        if(c->tsmeQuality >= 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its TSME encoder");
-        if(c->cfOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: the context post-processes with its crossfeed");
-        if(!c->decOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: needs a B-Format decoder (oalgpu_set_bformat_decoder)");
-        const uint32_t nr = c->L.numReal;
-        if(nr > 32u || params->left >= nr || params->right >= nr || params->center >= nr || params->left == params->right
-            || params->left == params->center || params->right == params->center)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: left, right and center are three different real output lines");
-        if(!StabilizerDerive(params->xover_norm, &k))
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_front_stabilizer: needs 0 < xover_norm < 0.5");
-    }
-    // the kernels of the updates in flight are through with the old state before it goes
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->stabOn = false;
-    if(params)
-    {
-        const std::vector<float> init(kStabilizerStateFloats, 0.0f);
-        HIP_TRY(c->stabState.alloc(init.size()));
-        HIP_TRY(c->stabState.upload(init.data(), init.size()));
-        c->stab = k;
-        c->stabLeft = params->left; c->stabRight = params->right; c->stabCenter = params->center;
-        c->stabOn = true;
-    }
-    return OALGPU_OK;
-}
-
-// in front of the decode: the direct L / R signal moves out of the stabilizer's way (alu.cpp:339-348)
-int RunStabilizerSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(!c->stabOn) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    LaunchStabilizerSplit(s, L.bus + size_t{L.numDry} * kLine, c->stabLeft, c->stabRight, samplesToDo, c->stabState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-// behind the decode: the band split of the decoded mid, the all-passes, the combine (alu.cpp:353-404)
-int RunStabilizer(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(!c->stabOn) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    LaunchStabilizer(s, L.bus + size_t{L.numDry} * kLine, L.numReal, c->stabLeft, c->stabRight, c->stabCenter, samplesToDo, c->stab,
-        c->stabState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-/* The stereo TSME encoder (TsmePostProcess, alc/alu.cpp:314-327): the quality's taps (the UHJ encoder's: the same
- * SegmentedFilter<N>), a fresh state, and from the next update on the encode behind every post-process (RunTsmeEncoder) */
-uint32_t oalgpu_tsme_encoder_delay(int quality) { return UhjEncoderDelay(quality); }       // (TsmeEncoder*::getDelay: the same three)
-
-int oalgpu_set_tsme_encoder(oalgpu_context *c, int quality)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: null context");
-    if(quality >= 0)
-    {
-        if(UhjEncoderDelay(quality) == 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: not a TSME quality");
-        if(c->L.hrtf)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: an HRTF context post-processes with MixDirectHrtf");
-        if(c->L.numDry != 4 || c->L.numReal != 2)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: needs four dry lines (W, Y, Z, X) and two real output lines");
-        if(c->decOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its B-Format decoder");
-        if(c->uhjQuality >= 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its UHJ encoder");
-        if(c->stabOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its front stabilizer");
-        if(c->cfOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_tsme_encoder: the context post-processes with its crossfeed");
-    }
-    // the kernels of the updates in flight are through with the old state before it goes
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->tsmeQuality = -1;
-    if(quality >= 0)
-    {
-        if(const uint32_t len = UhjFirLength(quality))
-        {
-            const std::vector<float> taps = UhjFirTaps(len);
-            HIP_TRY(c->tsmeTaps.alloc(taps.size()));
-            HIP_TRY(c->tsmeTaps.upload(taps.data(), taps.size()));
-        }
-        const std::vector<float> init(UhjStateFloats(quality), 0.0f);
-        HIP_TRY(c->tsmeState.alloc(init.size()));
-        HIP_TRY(c->tsmeState.upload(init.data(), init.size()));
-        c->tsmeQuality = quality;
-    }
-    return OALGPU_OK;
-}
-
-// TsmeEncoder*::encode behind the update's effect slots, on the stream that runs the post-process: dry lines 0-3 (W, Y, Z, X) in,
-// the two real output lines (FrontLeft, FrontRight) delayed and added to
-int RunTsmeEncoder(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(c->tsmeQuality < 0) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    float *left = L.bus + size_t{L.numDry} * kLine;
-    LaunchTsmeEncode(s, c->tsmeQuality, left, left + kLine, L.bus, samplesToDo, c->tsmeTaps.p, c->tsmeState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-/* The bs2b crossfeed (Bs2bPostProcess, alc/alu.cpp:407-434; bs2b_processor::set_params, core/bs2b.cpp): the level's constants
- * at the context's sample rate (host/crossfeed_params.cpp), a fresh state, and from the next update on RunCrossfeedSplit /
- * RunCrossfeed around the decode of every post-process */
-int oalgpu_crossfeed_constants(int level, uint32_t sample_rate, float *out)
-{
-    CrossfeedConsts k{};
-    if(!out || !CrossfeedDerive(level, sample_rate, &k))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_crossfeed_constants: needs a level of 1 to 6 and a sample rate");
-    out[0] = k.a0Lo; out[1] = k.b1Lo; out[2] = k.a0Hi; out[3] = k.a1Hi; out[4] = k.b1Hi;
-    return OALGPU_OK;
-}
-
-int oalgpu_set_crossfeed(oalgpu_context *c, int level, uint32_t left, uint32_t right)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: null context");
-    CrossfeedConsts k{};
-    if(level != 0)
-    {
-        if(!CrossfeedDerive(level, c->desc.sample_rate, &k))
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: not a crossfeed level (1 to 6; 0 removes)");
-        if(c->L.hrtf)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: an HRTF context post-processes with MixDirectHrtf");
-        if(c->uhjQuality >= 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: the context post-processes with its UHJ encoder");
-        if(c->tsmeQuality >= 0)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: the context post-processes with its TSME encoder");
-        if(c->stabOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: the context post-processes with its front stabilizer");
-        if(!c->decOn)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: needs a B-Format decoder (oalgpu_set_bformat_decoder)");
-        if(left >= c->L.numReal || right >= c->L.numReal || left == right)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_crossfeed: left and right are two different real output lines");
-    }
-    // the kernels of the updates in flight are through with the old state before it goes
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->cfOn = false;
-    if(level != 0)
-    {
-        const std::vector<float> init(kCrossfeedStateFloats, 0.0f);
-        HIP_TRY(c->cfState.alloc(init.size()));
-        HIP_TRY(c->cfState.upload(init.data(), init.size()));
-        c->cf = k;
-        c->cfLeft = left; c->cfRight = right;
-        c->cfOn = true;
-    }
-    return OALGPU_OK;
-}
-
-// in front of the decode: the direct L / R signal moves out of the filter's way (alu.cpp:416-423)
-int RunCrossfeedSplit(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(!c->cfOn) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    LaunchCrossfeedSplit(s, L.bus + size_t{L.numDry} * kLine, c->cfLeft, c->cfRight, samplesToDo, c->cfState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-// behind the decode: cross_feed over the decoded left and right lines, the direct signal added back (alu.cpp:429-433)
-int RunCrossfeed(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(!c->cfOn) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    LaunchCrossfeed(s, L.bus + size_t{L.numDry} * kLine, c->cfLeft, c->cfRight, samplesToDo, c->cf, c->cfState.p);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
-/* Speaker distance compensation (ApplyDistanceComp, alc/alu.cpp:2276-2307; InitDistanceComp, alc/panning.cpp:301-371): per
- * output line a delay and a gain, fresh (zero) delay lines, and from the next update on RunDistanceComp behind the limiter */
-int oalgpu_distance_comp_from_distances(uint32_t sample_rate, const float *distances, uint32_t n, uint32_t *delays, float *gains)
-{
-    if(sample_rate == 0 || !distances || !delays || !gains || n == 0 || n > 32u)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_distance_comp_from_distances: bad arguments");
-    return DistanceCompDerive(sample_rate, distances, n, delays, gains) ? 1 : 0;
-}
-
-int oalgpu_set_distance_comp(oalgpu_context *c, uint32_t n, const uint32_t *delays, const float *gains)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c) return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: null context");
-    const bool set = n != 0 && delays && gains;
-    if(set)
-    {
-        if(c->L.hrtf)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: an HRTF context has no speaker distances to compensate");
-        if(n > (c->L.numReal ? c->L.numReal : c->L.numDry))
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: more channels than the context has output lines");
-        for(uint32_t i = 0; i < n; ++i)
-            if(delays[i] > kDistCompMaxDelay)
-                return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: a delay of more than 1023 samples");
-    }
-    // the kernels of the updates in flight are through with the old delay lines before they go
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->distLines = 0;
-    if(set)
-    {
-        HIP_TRY(c->distDelays.alloc(n)); HIP_TRY(c->distDelays.upload(delays, n));
-        HIP_TRY(c->distGains.alloc(n)); HIP_TRY(c->distGains.upload(gains, n));
-        const std::vector<float> init(size_t{n} * kLine, 0.0f);
-        HIP_TRY(c->distHist.alloc(init.size())); HIP_TRY(c->distHist.upload(init.data(), init.size()));
-        c->distLines = n;
-    }
-    return OALGPU_OK;
-}
-
-// ApplyDistanceComp behind the limiter, on the stream that ran it (alc/alu.cpp:2449-2450), over the limiter's line set
-int RunDistanceComp(oalgpu_context *c, hipStream_t s, uint32_t samplesToDo)
-{
-    if(!c->distLines) return OALGPU_OK;
-    const DeviceLayout &L = c->L;
-    LaunchDistanceComp(s, L.numReal ? L.bus + size_t{L.numDry} * kLine : L.bus, c->distLines, samplesToDo, c->distDelays.p,
-        c->distGains.p, c->distHist.p);
-    HIP_TRY(hipGetLastError());
     return OALGPU_OK;
 }
 
@@ -606,11 +191,9 @@ int oalgpu_read_output(oalgpu_context *c, void *out, uint32_t samples_to_do, uin
         return Fail(OALGPU_ERR_INVALID, "oalgpu_read_output: bad arguments");
     if(int rc = UseCtx(c)) return rc;
     if(int rc = JoinPost(c)) return rc;
-    const DeviceLayout &L = c->L;
-    // RealOut: the real output lines, or the dry lines themselves where the device has none (core/device.h:300)
-    float *lines = L.numReal ? L.bus + size_t{L.numDry} * kLine : L.bus;
-    const uint32_t nlines = std::min(L.numReal ? L.numReal : L.numDry, frame_step);
-    const uint32_t all = L.numReal ? L.numReal : L.numDry;
+    float *lines = RealOut(c);
+    const uint32_t all = RealOutLines(c);
+    const uint32_t nlines = std::min(all, frame_step);
     if(c->ditherDepth > 0.0f)
     {
         LaunchDither(c->stream, lines, all, samples_to_do, c->ditherDepth, c->ditherSeed);
@@ -645,10 +228,8 @@ int oalgpu_read_hrtf_accum(oalgpu_context *c, float *out)
 
 int oalgpu_bus_device_ptr(oalgpu_context *c, void **ptr, size_t *nfloats, void **hip_stream)
 {
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c || !ptr || !nfloats) return Fail(OALGPU_ERR_INVALID, "null argument");
+    if(int rc = BeginSetter(c, "oalgpu_bus_device_ptr")) return rc;
+    if(!ptr || !nfloats) return Fail(OALGPU_ERR_INVALID, "null argument");
     *ptr = c->L.bus;
     *nfloats = BusFloats(c->L);
     if(hip_stream)      // the pipelined path produces the bus on the post stream, the serial entry points on the main one
