@@ -334,6 +334,7 @@ int AllocStreamRows(oalgpu_context *c)
     return OALGPU_OK;
 }
 
+static const float *SlotWetBus(const DeviceLayout &L, uint32_t slot) { return L.bus + BusWetOffset(L) + size_t{slot} * L.wetChannels * kLine; }
 // EffectState::process of every slot that has an effect attached (alc/alu.cpp:2209-2257): from
 // channel 0 of the slot's wet bus into the dry lines, on stream `s`, after the buses are final.
 static int RunEffects(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
@@ -341,7 +342,7 @@ static int RunEffects(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
     const DeviceLayout &L = c->L;
     for(uint32_t slot = 0; slot < L.numSlots; ++slot)
     {
-        const float *wet = L.bus + BusWetOffset(L) + size_t{slot} * L.wetChannels * kLine;
+        const float *wet = SlotWetBus(L, slot);
         if(oalgpu_convolution *conv = c->slotConv[slot])
         {
             if(int rc = oalgpu_convolution_process_device(conv, s, wet, L.bus, samples_to_do)) return rc;
@@ -366,7 +367,7 @@ static int RunEffects(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
     {
         if(!c->slotReverb[slot]) continue;
         revs[count] = c->slotReverb[slot];
-        wets[count] = L.bus + BusWetOffset(L) + size_t{slot} * L.wetChannels * kLine;
+        wets[count] = SlotWetBus(L, slot);
         if(++count == kRvBatchMax) { if(int rc = flush()) return rc; }
     }
     if(int rc = flush()) return rc;
@@ -1005,6 +1006,9 @@ int oalgpu_slot_set_convolution(oalgpu_context *c, uint32_t slot, oalgpu_convolu
     return OALGPU_OK;
 }
 
+static uint32_t AttachedReverbs(const oalgpu_context *c)
+{ return uint32_t(c->slotReverb.size() - std::count(c->slotReverb.begin(), c->slotReverb.end(), nullptr)); }
+
 // An EAX reverb instance is ONE workgroup that needs a compute unit's LDS nearly to itself (128 KB: both pipelines' rows,
 // csrc/reverb_kernels.hip), and it runs on the post stream beside the NEXT update's voice kernel.  A voice kernel whose grid fills
 // the machine exactly (two 78 KB workgroups on every CU) then finds the instances' CUs taken: the workgroups it cannot place wait
@@ -1017,8 +1021,7 @@ int oalgpu_slot_set_convolution(oalgpu_context *c, uint32_t slot, oalgpu_convolu
 static void SetRowsGroups(oalgpu_context *c)
 {
     DeviceLayout &L = c->L;
-    uint32_t reverbs = 0;
-    for(oalgpu_reverb *r : c->slotReverb) reverbs += r ? 1u : 0u;
+    const uint32_t reverbs = AttachedReverbs(c);
     const uint32_t cus = DeviceComputeUnits(c->desc.device);
     const uint32_t waves = RowsWavesPerGroup();
     uint32_t groups = std::min<uint32_t>(cus > reverbs ? cus - reverbs : 1u, (L.numVoices + waves - 1u) / waves);
@@ -1046,8 +1049,7 @@ static int RebalanceWaveGroups(oalgpu_context *c)
         return OALGPU_OK;
     }
     if(!c->useWave || c->desc.voices_per_group != 0u || c->L.wave16) return OALGPU_OK;
-    uint32_t reverbs = 0;
-    for(oalgpu_reverb *r : c->slotReverb) reverbs += r ? 1u : 0u;
+    const uint32_t reverbs = AttachedReverbs(c);
     hipDeviceProp_t prop{};
     if(hipGetDeviceProperties(&prop, c->desc.device) != hipSuccess || prop.multiProcessorCount <= 0) { (void)hipGetLastError(); return OALGPU_OK; }
     const uint32_t cus = uint32_t(prop.multiProcessorCount);

@@ -46,6 +46,7 @@ struct DevBuf {
     hipError_t upload(const T *src, size_t count) { return hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice); }
     hipError_t download(T *dst, size_t count) const { return hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost); }
     hipError_t zero() { return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)); }
+    hipError_t alloc_zero(size_t count) { const hipError_t err = alloc(count); return err != hipSuccess ? err : zero(); }
 };
 
 } // namespace oalgpu

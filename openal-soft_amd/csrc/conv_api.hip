@@ -165,18 +165,18 @@ int oalgpu_convolution_create_ex(int device, uint32_t num_out_lines, const float
     HIP_TRY(c->filt.alloc(filt.size())); HIP_TRY(c->filt.upload(filt.data(), filt.size()));
     HIP_TRY(c->tw128.alloc(128)); HIP_TRY(c->tw128.upload(tw128.data(), 128));
     HIP_TRY(c->tw256.alloc(256)); HIP_TRY(c->tw256.upload(tw256.data(), 256));
-    HIP_TRY(c->xhist.alloc(kFftLen)); HIP_TRY(c->xhist.zero());
-    HIP_TRY(c->ring.alloc(size_t{c->ringSlots} * kFftLen)); HIP_TRY(c->ring.zero());
-    HIP_TRY(c->outFifo.alloc(size_t{channels} * kFftLen)); HIP_TRY(c->outFifo.zero());
-    HIP_TRY(c->partial.alloc(size_t{channels} * c->numChunks * 8 * kFftLen)); HIP_TRY(c->partial.zero());
-    HIP_TRY(c->ticket.alloc(16)); HIP_TRY(c->ticket.zero());
-    HIP_TRY(c->firOut.alloc(size_t{channels} * OALGPU_BUFFER_LINE_SIZE)); HIP_TRY(c->firOut.zero());
-    HIP_TRY(c->chanOut.alloc(size_t{channels} * OALGPU_BUFFER_LINE_SIZE)); HIP_TRY(c->chanOut.zero());
-    HIP_TRY(c->cur.alloc(size_t{channels} * num_out_lines)); HIP_TRY(c->cur.zero());
-    HIP_TRY(c->tgt.alloc(size_t{channels} * num_out_lines)); HIP_TRY(c->tgt.zero());
-    HIP_TRY(c->split.alloc(channels)); HIP_TRY(c->split.zero());
-    HIP_TRY(c->hfScale.alloc(channels)); HIP_TRY(c->hfScale.zero());
-    HIP_TRY(c->lfScale.alloc(channels)); HIP_TRY(c->lfScale.zero());
+    HIP_TRY(c->xhist.alloc_zero(kFftLen));
+    HIP_TRY(c->ring.alloc_zero(size_t{c->ringSlots} * kFftLen));
+    HIP_TRY(c->outFifo.alloc_zero(size_t{channels} * kFftLen));
+    HIP_TRY(c->partial.alloc_zero(size_t{channels} * c->numChunks * 8 * kFftLen));
+    HIP_TRY(c->ticket.alloc_zero(16));
+    HIP_TRY(c->firOut.alloc_zero(size_t{channels} * OALGPU_BUFFER_LINE_SIZE));
+    HIP_TRY(c->chanOut.alloc_zero(size_t{channels} * OALGPU_BUFFER_LINE_SIZE));
+    HIP_TRY(c->cur.alloc_zero(size_t{channels} * num_out_lines));
+    HIP_TRY(c->tgt.alloc_zero(size_t{channels} * num_out_lines));
+    HIP_TRY(c->split.alloc_zero(channels));
+    HIP_TRY(c->hfScale.alloc_zero(channels));
+    HIP_TRY(c->lfScale.alloc_zero(channels));
     HIP_TRY(c->hostIn.alloc(OALGPU_BUFFER_LINE_SIZE));
     HIP_TRY(c->hostOut.alloc(size_t{num_out_lines} * OALGPU_BUFFER_LINE_SIZE));
     *out = c.release();

@@ -1,85 +1,90 @@
 // C-ABI of the small EffectStates (include/oalgpu.h: oalgpu_effect_*): deviceUpdate / update as the reference does
 // them on its mixer thread with libm -- biquad design, the echo's delays, the modulator's carrier period -- and the
 // scalar bookkeeping process() performs (delay-line offset, carrier index); the block itself is one launch
-// (effects_kernels.hip).
+// (effects_kernels.hip, effects2_kernels.hip).  Each kind is described once: what it owns in oalgpu_effect, its
+// DeviceUpdate / Update / Begin / Advance functions, and its row of kKinds, which every entry point dispatches through.
 #include "api_util.hpp"
 #include "kernels.hpp"
 #include "../host/params.hpp"
 #include "../host/tables.hpp"
 
 #include <cmath>
-#include <cstring>
 #include <memory>
 #include <vector>
 
 using namespace oalgpu;
 
+struct FxHop { uint32_t count, pos; };   // the fill counter of a shifter's STFT (mCount / mPos), moved on by AdvanceHop
+
 struct oalgpu_effect {
     int device{0}, kind{0};
-    bool exact{false};
     uint32_t sampleRate{48000}, numIn{1}, nlines{1};
     bool updated{false};
-    DevBuf<FxState> st;
-    DevBuf<float> tgtGains, delay, hostIn, hostOut;
-    FxLaunch F{};
-    // ModulatorState::mIndex / mRange (modulator.cpp:75-77), EchoState::mOffset (echo.cpp:55)
-    uint32_t modIndex{0}, modRange{1};
-    uint32_t echoOffset{0};
-    // ---- chorus .. frequency shifter (effects2_kernels.hip) ----
-    DevBuf<Fx2State> st2;
-    DevBuf<float> cubic, upTgt, window;
-    DevBuf<double> fsIn;
-    DevBuf<FsPair> fsOutFifo, fsAccum, fsOutdata, fsTw, fsPhase;
-    DevBuf<float> psRing, psPhase, psAccum, psOutFifo, psRows, psTw;     // psRing / psPhase: two copies, read [parity], written [parity ^ 1]
-    Fx2Launch G{};
+    DevBuf<FxState> st;                  // equalizer .. compressor (effects_kernels.hip)
+    DevBuf<Fx2State> st2;                // chorus .. pitch shifter (effects2_kernels.hip)
+    DevBuf<float> tgtGains, upTgt, hostIn, hostOut;
+    FxLaunch F{}; Fx2Launch G{};
+    // ---- what each kind owns besides ----
+    struct { uint32_t index{0}, range{1}; } modulator;                   // ModulatorState::mIndex / mRange (modulator.cpp:75-77)
+    struct { uint32_t offset{0}; DevBuf<float> line; } echo;             // EchoState::mOffset (echo.cpp:55)
     // ChorusState::mOffset / mLfoOffset / mLfoRange / mLfoDisp (chorus.cpp:83-88)
-    uint32_t chOffset{0}, lfoOffset{0}, lfoRange{1}, lfoDisp{0};
-    // VmorpherState::mIndex (vmorpher.cpp:152); FshifterState::mCount / mPos / mChans[c].mPhase (fshifter.cpp:100-113)
-    uint32_t vmIndex{0};
-    uint32_t fsCount{0}, fsPos{768}, fsPhase4[4]{};
-    // PshifterState::mCount / mPos (pshifter.cpp:86-87)
-    uint32_t psCount{0}, psPos{1024 - 128}, psParity{0};
+    struct { uint32_t offset{0}, lfoOffset{0}, lfoRange{1}, lfoDisp{0}; DevBuf<float> line, cubic; } chorus;
+    struct { uint32_t index{0}; } vmorpher;                              // VmorpherState::mIndex (vmorpher.cpp:152)
+    struct {                                                             // FshifterState::mCount / mPos / mChans[c].mPhase (fshifter.cpp:100-113)
+        FxHop hop{0, 1024 - 256};
+        uint32_t phase4[4]{};
+        DevBuf<double> in; DevBuf<FsPair> outFifo, accum, outdata, tw, phase; DevBuf<float> window;
+    } fshifter;
+    struct {                                                             // PshifterState::mCount / mPos (pshifter.cpp:86-87)
+        FxHop hop{0, 1024 - 128};
+        uint32_t parity{0};
+        DevBuf<float> ring, phase, accum, outFifo, rows, tw, window;     // ring / phase: two copies, read [parity], written [parity ^ 1]
+    } pshifter;
 };
 
 namespace {
 
-int UploadBiquad(oalgpu_effect *e, uint32_t chan, uint32_t which, const float c[5])
-{   // copyParamsFrom / setParams: the coefficients change, the filter's history stays
-    float five[5] = {c[0], c[1], c[2], c[3], c[4]};
-    char *dst = reinterpret_cast<char*>(e->st.p) + offsetof(FxState, bq) + (size_t{chan} * 4 + which) * sizeof(BiquadState)
-        + offsetof(BiquadState, b0);
-    HIP_TRY(hipMemcpy(dst, five, sizeof(five), hipMemcpyHostToDevice));
-    return OALGPU_OK;
-}
-
-uint32_t NextPow2(uint32_t v) { uint32_t p = 1; while(p < v) p <<= 1; return p; }
-
-bool IsFx2(int kind) { return kind >= OALGPU_EFFECT_CHORUS && kind <= OALGPU_EFFECT_PSHIFTER; }
-
-// float2int / float2uint (common/alnumeric.h): truncation
-int32_t TruncI(float f) { return static_cast<int32_t>(f); }
-uint32_t TruncU(float f) { return static_cast<uint32_t>(static_cast<int64_t>(f)); }
-// fastf2u: round to nearest even (cvtss2si)
-uint32_t RoundU(float f) { return static_cast<uint32_t>(static_cast<int32_t>(std::lrintf(f))); }
+constexpr double kPi = 3.14159265358979323846; constexpr float kPiF = 3.14159265358979323846f;
 
 template<typename T>
 int UploadAt(void *base, size_t offset, const T *src, size_t count)
-{
-    HIP_TRY(hipMemcpy(static_cast<char*>(base) + offset, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return OALGPU_OK;
+{ HIP_TRY(hipMemcpy(static_cast<char*>(base) + offset, src, count * sizeof(T), hipMemcpyHostToDevice)); return OALGPU_OK; }
+
+int UploadBiquad(oalgpu_effect *e, uint32_t chan, uint32_t which, const float c[5])
+{   // copyParamsFrom / setParams: the coefficients change, the filter's history stays
+    return UploadAt(e->st.p, offsetof(FxState, bq) + (size_t{chan} * 4 + which) * sizeof(BiquadState) + offsetof(BiquadState, b0), c, 5);
 }
 
+uint32_t NextPow2(uint32_t v) { uint32_t p = 1; while(p < v) p <<= 1; return p; }
+// float2int / float2uint (common/alnumeric.h): truncation; fastf2u: round to nearest even (cvtss2si)
+int32_t TruncI(float f) { return static_cast<int32_t>(f); }
+uint32_t TruncU(float f) { return static_cast<uint32_t>(static_cast<int64_t>(f)); }
+uint32_t RoundU(float f) { return static_cast<uint32_t>(static_cast<int32_t>(std::lrintf(f))); }
+
 // gHannWindow<1024>, common/hann_window.hpp: sin^2 through double, mirrored
-std::vector<float> HannWindow1024()
+int UploadHannWindow1024(DevBuf<float> &window)
 {
     std::vector<float> win(1024);
-    const double scale = 3.14159265358979323846 / double(1024 + 1);
+    const double scale = kPi / double(1024 + 1);
     for(uint32_t i = 0; i < 512; ++i)
     {
         const double v = std::sin((i + 1.0) * scale);
         win[i] = win[1023 - i] = static_cast<float>(v * v);
     }
-    return win;
+    HIP_TRY(window.alloc(win.size())); HIP_TRY(window.upload(win.data(), win.size()));
+    return OALGPU_OK;
+}
+
+// `n` more samples into an STFT that transforms whenever `hop` have come in and then moves on in its 1024-sample FIFO
+void AdvanceHop(FxHop &h, uint32_t hop, uint32_t n)
+{
+    for(uint32_t base = 0; base < n;)
+    {
+        const uint32_t todo = std::min(hop - h.count, n - base);
+        h.count += todo; base += todo;
+        if(h.count < hop) break;
+        h.count = 0; h.pos = (h.pos + hop) & 1023u;
+    }
 }
 
 #pragma clang fp contract(off)
@@ -117,148 +122,344 @@ void BuildTwiddles(std::vector<FsPair> &tw)
     }
 }
 
+// ---- Per kind: the functions of KindInfo (below), named after the reference's members ----
 
-// update() of the chorus / distortion / autowah / vocal morpher / frequency shifter states
-int UpdateFx2(oalgpu_effect *e, const void *props, const uint32_t *target_channels, const float *gains)
-{
-    if(!props || !target_channels) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: this effect needs props and targets");
-    const float rate = float(e->sampleRate);
-    Fx2Launch &G = e->G;
-    const bool aformat = e->kind == OALGPU_EFFECT_CHORUS || e->kind == OALGPU_EFFECT_DISTORTION || e->kind == OALGPU_EFFECT_FSHIFTER;
-    switch(e->kind)
-    {
-    case OALGPU_EFFECT_CHORUS:
-        {   // ChorusState::update, chorus.cpp:165-251
-            const auto &p = *static_cast<const oalgpu_chorus_props*>(props);
-            const int32_t mindelay = 24 << 8;                       // MaxResamplerEdge << gCubicTable.sTableBits
-            const float stepscale = rate * 256.0f;
-            G.chWave = p.waveform;
-            G.chDelay = std::max(TruncI(std::round(p.delay * stepscale)), mindelay);
-            G.chDepth = std::min(float(G.chDelay) * p.depth, float(G.chDelay - mindelay));
-            G.chFeedback = p.feedback;
-            if(!(p.rate > 0.0f)) { e->lfoOffset = 0; e->lfoRange = 1; G.lfoScale = 0.0f; e->lfoDisp = 0; }
-            else
-            {
-                const int32_t rangeLimit = 2147483647 / 360 - 180;
-                const float range = std::round(rate / p.rate);
-                const uint32_t lfoRange = TruncU(std::min(range, float(rangeLimit)));
-                e->lfoOffset = e->lfoOffset * lfoRange / e->lfoRange;
-                e->lfoRange = lfoRange;
-                G.lfoScale = (p.waveform == OALGPU_CHORUS_TRIANGLE) ? 4.0f / float(lfoRange)
-                    : 3.14159265358979323846f * 2.0f / float(lfoRange);
-                int32_t phase = p.phase;
-                if(phase < 0) phase += 360;
-                e->lfoDisp = (lfoRange * uint32_t(phase) + 180u) / 360u;
-            }
-            G.lfoRange = e->lfoRange;
-            G.chAvgDelay = (uint32_t(G.chDelay) + 32768u) >> 16;         // (mDelay + MixerFracHalf) >> MixerFracBits
-            // how far behind the write position a tap or the feedback reads
-            const uint32_t maxTap = (uint32_t(G.chDelay) + uint32_t(std::ceil(G.chDepth)) + 1u) >> 8;
-            G.chHist = std::max(maxTap + 3u, G.chAvgDelay);
-            if(G.chHist > G.delayMask) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: chorus delay beyond the delay line");
-        }
-        break;
-    case OALGPU_EFFECT_DISTORTION:
-        {   // DistortionState::update, distortion.cpp:141-195 (the filters work on the 4x oversampled signal)
-            const auto &p = *static_cast<const oalgpu_distortion_props*>(props);
-            const float edge = std::min(std::sin(3.14159265358979323846f * 0.5f * p.edge), 0.99f);
-            G.edgeCoeff = 2.0f * edge / (1.0f - edge);
-            float lp[5], bp[5];
-            DesignBiquadFromBandwidth(OALGPU_BIQUAD_LOWPASS, p.lowpass_cutoff / rate * 0.25f, 1.0f, 0.746268656716f, lp);
-            const float bandwidth = p.eq_bandwidth / (p.eq_center * 0.67f);
-            DesignBiquadFromBandwidth(OALGPU_BIQUAD_BANDPASS, p.eq_center / rate * 0.25f, 1.0f, bandwidth, bp);
-            for(uint32_t c = 0; c < 4; ++c)
-            {
-                if(int rc = UploadAt(e->st2.p, offsetof(Fx2State, lp) + c * sizeof(BiquadState) + offsetof(BiquadState, b0), lp, 5)) return rc;
-                if(int rc = UploadAt(e->st2.p, offsetof(Fx2State, bp) + c * sizeof(BiquadState) + offsetof(BiquadState, b0), bp, 5)) return rc;
-            }
-        }
-        break;
-    case OALGPU_EFFECT_AUTOWAH:
-        {   // AutowahState::update, autowah.cpp:100-122
-            const auto &p = *static_cast<const oalgpu_autowah_props*>(props);
-            const float release = std::min(std::max(p.release_time, 0.001f), 1.0f);
-            G.attackRate = std::exp(-1.0f / (p.attack_time * rate));
-            G.releaseRate = std::exp(-1.0f / (release * rate));
-            G.resonanceGain = std::sqrt(std::log10(p.resonance) * 10.0f / 3.0f);
-            G.peakGain = 1.0f - std::log10(p.peak_gain / 31621.0f);
-            G.freqMinNorm = 20.0f / rate;
-            G.bandwidthNorm = (2500.0f - 20.0f) / rate;
-        }
-        break;
-    case OALGPU_EFFECT_VMORPHER:
-        {   // VmorpherState::update, vmorpher.cpp:234-277; getFiltersByPhoneme :164-226
-            const auto &p = *static_cast<const oalgpu_vmorpher_props*>(props);
-            const float step = p.rate / rate;
-            G.vmStep = RoundU(std::min(std::max(step * 16777216.0f, 0.0f), 16777216.0f - 1.0f));
-            G.vmWave = G.vmStep == 0 ? 0 : p.waveform == OALGPU_VMORPHER_SINUSOID ? 1 : p.waveform == OALGPU_VMORPHER_TRIANGLE ? 2 : 3;
-            static const float kFreq[5][4] = {{800, 1150, 2900, 3900}, {350, 2000, 2800, 3600}, {270, 2140, 2950, 3900},
-                {450, 800, 2830, 3800}, {325, 700, 2700, 3800}};
-            static const float kGain[5][4] = {{1.000000f, 0.501187f, 0.025118f, 0.100000f}, {1.000000f, 0.100000f, 0.177827f, 0.009999f},
-                {1.000000f, 0.251188f, 0.050118f, 0.050118f}, {1.000000f, 0.281838f, 0.079432f, 0.079432f},
-                {1.000000f, 0.158489f, 0.017782f, 0.009999f}};
-            const int32_t ph[2] = {p.phoneme_a, p.phoneme_b}, tune[2] = {p.phoneme_a_coarse_tuning, p.phoneme_b_coarse_tuning};
-            for(int v = 0; v < 2; ++v)
-            {
-                const float pitch = std::pow(2.0f, float(tune[v]) / 12.0f);
-                for(int k = 0; k < 4; ++k)
-                {
-                    if(ph[v] >= 0 && ph[v] < 5)
-                    {   // FormantFilter(f0norm, gain): mCoeff = tan(pi * f0norm)
-                        G.vmG[v * 4 + k] = std::tan(3.14159265358979323846f * ((kFreq[ph[v]][k] * pitch) / rate));
-                        G.vmGain[v * 4 + k] = kGain[ph[v]][k];
-                    }
-                    else { G.vmG[v * 4 + k] = 0.0f; G.vmGain[v * 4 + k] = 1.0f; }       // the other phonemes: FormantFilter{}
-                }
-            }
-            // the copies of the new filters start with cleared histories, for every wet channel
-            std::vector<float> zeros(size_t{e->numIn} * 16, 0.0f);
-            if(int rc = UploadAt(e->st2.p, offsetof(Fx2State, vmS), zeros.data(), zeros.size())) return rc;
-        }
-        break;
-    case OALGPU_EFFECT_PSHIFTER:
-        {   // PshifterState::update, pshifter.cpp:168-199
-            const auto &p = *static_cast<const oalgpu_pshifter_props*>(props);
-            const int32_t tune = p.coarse_tune * 100 + p.fine_tune;
-            const float pitch = std::pow(2.0f, float(tune) / 1200.0f);
-            G.psPitchI = RoundU(std::min(std::max(pitch, 0.5f), 2.0f) * 65536.0f);
-            G.psPitch = float(G.psPitchI) * (1.0f / 65536.0f);
-        }
-        break;
-    default:
-        {   // FshifterState::update, fshifter.cpp:162-214
-            const auto &p = *static_cast<const oalgpu_fshifter_props*>(props);
-            const float step = p.frequency / rate;
-            const uint32_t phaseStep = RoundU(std::min(step, 1.0f) * 65536.0f);
-            for(int c = 0; c < 4; ++c) G.fsPhaseStep[c] = phaseStep;
-            const int32_t dir[2] = {p.left_direction, p.right_direction};
-            for(int side = 0; side < 2; ++side)
-                for(int c = side * 2; c < side * 2 + 2; ++c)
-                {
-                    if(dir[side] == OALGPU_FSHIFTER_DOWN) G.fsSign[c] = -1.0;
-                    else if(dir[side] == OALGPU_FSHIFTER_UP) G.fsSign[c] = 1.0;
-                    else { e->fsPhase4[c] = 0; G.fsPhaseStep[c] = 0; }
-                }
-        }
-        break;
-    }
-    for(uint32_t ch = 0; ch < kFxMaxIn; ++ch) { G.target[ch] = OALGPU_INVALID_CHANNEL; G.tgtGain[ch] = 0.0f; }
-    const bool pshift = e->kind == OALGPU_EFFECT_PSHIFTER;
-    const uint32_t chans = aformat ? std::min(e->numIn, 4u) : pshift ? std::min(e->numIn, 9u) : e->numIn;
-    for(uint32_t ch = 0; ch < chans; ++ch) G.target[ch] = target_channels[ch];
-    if((aformat || pshift) && G.upsample)
-    {   // UpsampleParams::mTargetGains = ComputePanGains(target.Main, AmbiScale::FirstOrderUp[ch] (pitch shifter: SecondOrderUp[ch]),
-        // gain): gains[4 or 9][num_out_lines]
-        const uint32_t rows = pshift ? 9u : 4u;
-        std::vector<float> up(9 * 32, 0.0f);
-        for(uint32_t ch = 0; ch < rows; ++ch)
-            for(uint32_t l = 0; l < e->nlines; ++l) up[ch * 32 + l] = gains[size_t{ch} * e->nlines + l];
-        HIP_TRY(e->upTgt.upload(up.data(), up.size()));
-    }
-    else
-        for(uint32_t ch = 0; ch < chans; ++ch) G.tgtGain[ch] = gains[ch];
-    e->updated = true;
+int EqualizerUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // EqualizerState::update, equalizer.cpp:115-165
+    const auto &p = *static_cast<const oalgpu_equalizer_props*>(props);
+    float c[4][5];
+    DesignBiquadFromSlope(OALGPU_BIQUAD_LOWSHELF, p.low_cutoff / rate, std::sqrt(p.low_gain), 0.75f, c[0]);
+    DesignBiquadFromBandwidth(OALGPU_BIQUAD_PEAKING, p.mid1_center / rate, std::sqrt(p.mid1_gain), p.mid1_width, c[1]);
+    DesignBiquadFromBandwidth(OALGPU_BIQUAD_PEAKING, p.mid2_center / rate, std::sqrt(p.mid2_gain), p.mid2_width, c[2]);
+    DesignBiquadFromSlope(OALGPU_BIQUAD_HIGHSHELF, p.high_cutoff / rate, std::sqrt(p.high_gain), 0.75f, c[3]);
+    for(uint32_t ch = 0; ch < e->numIn; ++ch)
+        for(uint32_t k = 0; k < 4; ++k)
+            if(int rc = UploadBiquad(e, ch, k, c[k])) return rc;
     return OALGPU_OK;
+}
+
+int ModulatorUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // ModulatorState::update, modulator.cpp:103-163
+    const auto &p = *static_cast<const oalgpu_modulator_props*>(props);
+    FxLaunch &F = e->F; auto &m = e->modulator;
+    const float perCycle = p.frequency > 0.0f ? rate / p.frequency + 0.5f : 1.0f;
+    const uint32_t range = uint32_t(std::min(std::max(perCycle, 1.0f), rate));
+    m.index = uint32_t(uint64_t{m.index} * range / m.range);
+    m.range = range;
+    F.modScale = 0.0f; F.modWave = 0;
+    if(m.range == 1) {}
+    else if(p.waveform == OALGPU_MODULATOR_SINUSOID) { F.modScale = kPiF * 2.0f / float(m.range); F.modWave = 1; }
+    else if(p.waveform == OALGPU_MODULATOR_SAWTOOTH) { F.modScale = 2.0f / float(m.range - 1u); F.modWave = 2; }
+    else
+    {
+        m.range = (m.range + 1u) & ~1u;
+        F.modScale = 1.0f / float(m.range - 1u); F.modWave = 3;
+    }
+    const float f0norm = std::min(std::max(p.high_pass_cutoff / rate, 1.0f / 512.0f), 0.49f);
+    float c[5];
+    DesignBiquadFromBandwidth(OALGPU_BIQUAD_HIGHPASS, f0norm, 1.0f, 0.75f, c);
+    for(uint32_t ch = 0; ch < e->numIn; ++ch)
+        if(int rc = UploadBiquad(e, ch, 0, c)) return rc;
+    return OALGPU_OK;
+}
+int ModulatorBegin(oalgpu_effect *e, uint32_t&) { e->F.modIndex = e->modulator.index; e->F.modRange = e->modulator.range; return OALGPU_OK; }
+void ModulatorAdvance(oalgpu_effect *e, uint32_t n)           // modulator.cpp:176-189
+{ if(e->modulator.range > 1) e->modulator.index = (e->modulator.index + n) % e->modulator.range; }
+
+int EchoDeviceUpdate(oalgpu_effect *e, FxState&)
+{   // EchoState::deviceUpdate, echo.cpp:77-91: EchoMaxDelay 0.207 s + EchoMaxLRDelay 0.404 s, next power of two
+    const float f = float(e->sampleRate);
+    const uint32_t len = NextPow2(uint32_t(0.207f * f + 0.5f) + uint32_t(0.404f * f + 0.5f));
+    HIP_TRY(e->echo.line.alloc_zero(len));
+    e->F.delay = e->echo.line.p; e->F.delayMask = len - 1u;
+    return OALGPU_OK;
+}
+int EchoUpdate(oalgpu_effect *e, float rate, const void *props, const float *gains)
+{   // EchoState::update, echo.cpp:93-117 (the two taps' panned gains come from the caller)
+    const auto &p = *static_cast<const oalgpu_echo_props*>(props);
+    FxLaunch &F = e->F;
+    F.tap[0] = std::max(uint32_t(std::round(p.delay * rate)), 1u);
+    F.tap[1] = uint32_t(std::round(p.lr_delay * rate)) + F.tap[0];
+    if(F.tap[1] > F.delayMask) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: echo delays beyond AL_ECHO_MAX_DELAY + AL_ECHO_MAX_LRDELAY");
+    const float gainhf = std::max(1.0f - p.damping, 0.0625f);
+    float c[5];
+    DesignBiquadFromSlope(OALGPU_BIQUAD_HIGHSHELF, 5000.0f / rate, gainhf, 1.0f, c);
+    if(int rc = UploadBiquad(e, 0, 0, c)) return rc;
+    F.feedGain = p.feedback;
+    HIP_TRY(e->tgtGains.upload(gains, size_t{2} * e->nlines));
+    return OALGPU_OK;
+}
+int EchoBegin(oalgpu_effect *e, uint32_t&) { e->F.offset = e->echo.offset; return OALGPU_OK; }
+void EchoAdvance(oalgpu_effect *e, uint32_t n) { e->echo.offset = (e->echo.offset + n) & e->F.delayMask; }      // echo.cpp:127-157
+
+// DedicatedState::update, dedicated.cpp:66-100: the gains of the target line(s), resolved by the caller
+int DedicatedUpdate(oalgpu_effect *e, float, const void*, const float *gains) { HIP_TRY(e->tgtGains.upload(gains, e->nlines)); return OALGPU_OK; }
+
+int CompressorDeviceUpdate(oalgpu_effect *e, FxState &fresh)
+{   // CompressorState::deviceUpdate, compressor.cpp:87-101: 100 ms from 0.5 to 2, 200 ms back; mEnvFollower = 1
+    e->F.attackMult = std::pow(2.0f / 0.5f, 1.0f / (float(e->sampleRate) * 0.1f));
+    e->F.releaseMult = std::pow(0.5f / 2.0f, 1.0f / (float(e->sampleRate) * 0.2f));
+    fresh.env = 1.0f;
+    return OALGPU_OK;
+}
+int CompressorUpdate(oalgpu_effect *e, float, const void *props, const float*)
+{ e->F.compOn = static_cast<const oalgpu_compressor_props*>(props)->on_off ? 1 : 0; return OALGPU_OK; }
+
+int ChorusDeviceUpdate(oalgpu_effect *e, FxState&)
+{   // ChorusState::deviceUpdate, chorus.cpp:129-163: four lines of NextPowerOf2(2 * max(ChorusMaxDelay, FlangerMaxDelay) * rate + 1)
+    auto &ch = e->chorus;
+    const uint32_t len = NextPow2(TruncU(0.016f * 2.0f * float(e->sampleRate)) + 1u);
+    HIP_TRY(ch.line.alloc_zero(size_t{len} * 4));
+    HIP_TRY(ch.cubic.alloc(kFineCubicSteps * 2 + 1)); HIP_TRY(ch.cubic.upload(GetFineCubicFilter(), kFineCubicSteps * 2 + 1));
+    e->G.delay = ch.line.p; e->G.delayMask = len - 1u; e->G.cubic = ch.cubic.p;
+    return OALGPU_OK;
+}
+int ChorusUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // ChorusState::update, chorus.cpp:165-251
+    const auto &p = *static_cast<const oalgpu_chorus_props*>(props);
+    Fx2Launch &G = e->G; auto &ch = e->chorus;
+    const int32_t mindelay = 24 << 8;                       // MaxResamplerEdge << gCubicTable.sTableBits
+    const float stepscale = rate * 256.0f;
+    G.chWave = p.waveform;
+    G.chDelay = std::max(TruncI(std::round(p.delay * stepscale)), mindelay);
+    G.chDepth = std::min(float(G.chDelay) * p.depth, float(G.chDelay - mindelay));
+    G.chFeedback = p.feedback;
+    if(!(p.rate > 0.0f)) { ch.lfoOffset = 0; ch.lfoRange = 1; G.lfoScale = 0.0f; ch.lfoDisp = 0; }
+    else
+    {
+        const int32_t rangeLimit = 2147483647 / 360 - 180;
+        const float range = std::round(rate / p.rate);
+        const uint32_t lfoRange = TruncU(std::min(range, float(rangeLimit)));
+        ch.lfoOffset = ch.lfoOffset * lfoRange / ch.lfoRange;
+        ch.lfoRange = lfoRange;
+        G.lfoScale = (p.waveform == OALGPU_CHORUS_TRIANGLE) ? 4.0f / float(lfoRange)
+            : kPiF * 2.0f / float(lfoRange);
+        int32_t phase = p.phase;
+        if(phase < 0) phase += 360;
+        ch.lfoDisp = (lfoRange * uint32_t(phase) + 180u) / 360u;
+    }
+    G.lfoRange = ch.lfoRange;
+    G.chAvgDelay = (uint32_t(G.chDelay) + 32768u) >> 16;         // (mDelay + MixerFracHalf) >> MixerFracBits
+    // how far behind the write position a tap or the feedback reads
+    const uint32_t maxTap = (uint32_t(G.chDelay) + uint32_t(std::ceil(G.chDepth)) + 1u) >> 8;
+    G.chHist = std::max(maxTap + 3u, G.chAvgDelay);
+    if(G.chHist > G.delayMask) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: chorus delay beyond the delay line");
+    return OALGPU_OK;
+}
+int ChorusBegin(oalgpu_effect *e, uint32_t &lds)
+{
+    Fx2Launch &G = e->G; const auto &ch = e->chorus;
+    G.offset = ch.offset;
+    G.lfoStart[0] = ch.lfoOffset;
+    G.lfoStart[1] = (ch.lfoOffset + ch.lfoDisp) % ch.lfoRange;
+    lds = (6u * OALGPU_BUFFER_LINE_SIZE + G.chHist + OALGPU_BUFFER_LINE_SIZE) * sizeof(float);
+    if(lds > 65536u) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_process: chorus delay too long for the workgroup's LDS");
+    return OALGPU_OK;
+}
+void ChorusAdvance(oalgpu_effect *e, uint32_t n)              // chorus.cpp:283,391
+{ e->chorus.offset += n; e->chorus.lfoOffset = (e->chorus.lfoOffset + n) % e->chorus.lfoRange; }
+
+int DistortionDeviceUpdate(oalgpu_effect *e, FxState&)
+{   // mChans[c].mLowpass / mBandpass start as the identity
+    BiquadState ident{}; ident.b0 = 1.0f;
+    BiquadState eight[8]; for(auto &b : eight) b = ident;
+    return UploadAt(e->st2.p, offsetof(Fx2State, lp), eight, 8);
+}
+int DistortionUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // DistortionState::update, distortion.cpp:141-195 (the filters work on the 4x oversampled signal)
+    const auto &p = *static_cast<const oalgpu_distortion_props*>(props);
+    const float edge = std::min(std::sin(kPiF * 0.5f * p.edge), 0.99f);
+    e->G.edgeCoeff = 2.0f * edge / (1.0f - edge);
+    float lp[5], bp[5];
+    DesignBiquadFromBandwidth(OALGPU_BIQUAD_LOWPASS, p.lowpass_cutoff / rate * 0.25f, 1.0f, 0.746268656716f, lp);
+    const float bandwidth = p.eq_bandwidth / (p.eq_center * 0.67f);
+    DesignBiquadFromBandwidth(OALGPU_BIQUAD_BANDPASS, p.eq_center / rate * 0.25f, 1.0f, bandwidth, bp);
+    for(uint32_t c = 0; c < 4; ++c)
+    {
+        if(int rc = UploadAt(e->st2.p, offsetof(Fx2State, lp) + c * sizeof(BiquadState) + offsetof(BiquadState, b0), lp, 5)) return rc;
+        if(int rc = UploadAt(e->st2.p, offsetof(Fx2State, bp) + c * sizeof(BiquadState) + offsetof(BiquadState, b0), bp, 5)) return rc;
+    }
+    return OALGPU_OK;
+}
+
+int AutowahUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // AutowahState::update, autowah.cpp:100-122
+    const auto &p = *static_cast<const oalgpu_autowah_props*>(props);
+    Fx2Launch &G = e->G;
+    const float release = std::min(std::max(p.release_time, 0.001f), 1.0f);
+    G.attackRate = std::exp(-1.0f / (p.attack_time * rate));
+    G.releaseRate = std::exp(-1.0f / (release * rate));
+    G.resonanceGain = std::sqrt(std::log10(p.resonance) * 10.0f / 3.0f);
+    G.peakGain = 1.0f - std::log10(p.peak_gain / 31621.0f);
+    G.freqMinNorm = 20.0f / rate;
+    G.bandwidthNorm = (2500.0f - 20.0f) / rate;
+    return OALGPU_OK;
+}
+
+int VmorpherUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // VmorpherState::update, vmorpher.cpp:234-277; getFiltersByPhoneme :164-226
+    const auto &p = *static_cast<const oalgpu_vmorpher_props*>(props);
+    Fx2Launch &G = e->G;
+    const float step = p.rate / rate;
+    G.vmStep = RoundU(std::min(std::max(step * 16777216.0f, 0.0f), 16777216.0f - 1.0f));
+    G.vmWave = G.vmStep == 0 ? 0 : p.waveform == OALGPU_VMORPHER_SINUSOID ? 1 : p.waveform == OALGPU_VMORPHER_TRIANGLE ? 2 : 3;
+    static const float kFreq[5][4] = {{800, 1150, 2900, 3900}, {350, 2000, 2800, 3600}, {270, 2140, 2950, 3900},
+        {450, 800, 2830, 3800}, {325, 700, 2700, 3800}};
+    static const float kGain[5][4] = {{1.000000f, 0.501187f, 0.025118f, 0.100000f}, {1.000000f, 0.100000f, 0.177827f, 0.009999f},
+        {1.000000f, 0.251188f, 0.050118f, 0.050118f}, {1.000000f, 0.281838f, 0.079432f, 0.079432f},
+        {1.000000f, 0.158489f, 0.017782f, 0.009999f}};
+    const int32_t ph[2] = {p.phoneme_a, p.phoneme_b}, tune[2] = {p.phoneme_a_coarse_tuning, p.phoneme_b_coarse_tuning};
+    for(int v = 0; v < 2; ++v)
+    {
+        const float pitch = std::pow(2.0f, float(tune[v]) / 12.0f);
+        for(int k = 0; k < 4; ++k)
+        {
+            if(ph[v] >= 0 && ph[v] < 5)
+            {   // FormantFilter(f0norm, gain): mCoeff = tan(pi * f0norm)
+                G.vmG[v * 4 + k] = std::tan(kPiF * ((kFreq[ph[v]][k] * pitch) / rate));
+                G.vmGain[v * 4 + k] = kGain[ph[v]][k];
+            }
+            else { G.vmG[v * 4 + k] = 0.0f; G.vmGain[v * 4 + k] = 1.0f; }       // the other phonemes: FormantFilter{}
+        }
+    }
+    // the copies of the new filters start with cleared histories, for every wet channel
+    std::vector<float> zeros(size_t{e->numIn} * 16, 0.0f);
+    return UploadAt(e->st2.p, offsetof(Fx2State, vmS), zeros.data(), zeros.size());
+}
+int VmorpherBegin(oalgpu_effect *e, uint32_t&) { e->G.vmIndex = e->vmorpher.index; return OALGPU_OK; }
+void VmorpherAdvance(oalgpu_effect *e, uint32_t n)
+{   // vmorpher.cpp:293-294
+    for(uint32_t base = 0; base < n; base += 256u)
+        e->vmorpher.index = (e->vmorpher.index + e->G.vmStep * std::min(256u, n - base)) & 0xffffffu;
+}
+
+int FshifterDeviceUpdate(oalgpu_effect *e, FxState&)
+{   // FshifterState::deviceUpdate, fshifter.cpp:133-160; the Hann window of common/hann_window.hpp
+    Fx2Launch &G = e->G; auto &fs = e->fshifter;
+    HIP_TRY(fs.in.alloc_zero(4 * 1024));
+    HIP_TRY(fs.outFifo.alloc_zero(4 * 256));
+    HIP_TRY(fs.accum.alloc_zero(4 * 1024));
+    HIP_TRY(fs.outdata.alloc_zero(4 * OALGPU_BUFFER_LINE_SIZE));
+    std::vector<FsPair> tw; BuildTwiddles(tw);
+    HIP_TRY(fs.tw.alloc(tw.size())); HIP_TRY(fs.tw.upload(tw.data(), tw.size()));
+    // cos / sin of phase_idx * (pi*2 / MixerFracOne), fshifter.cpp:323-326: one entry per phase index
+    std::vector<FsPair> ph(65536);
+    for(uint32_t i = 0; i < 65536; ++i)
+    {
+        const double phase = i * (kPi * 2.0 / 65536.0);
+        ph[i] = FsPair{std::cos(phase), std::sin(phase)};
+    }
+    HIP_TRY(fs.phase.alloc(ph.size())); HIP_TRY(fs.phase.upload(ph.data(), ph.size()));
+    if(int rc = UploadHannWindow1024(fs.window)) return rc;
+    G.fsIn = fs.in.p; G.fsOutFifo = fs.outFifo.p; G.fsAccum = fs.accum.p; G.fsOutdata = fs.outdata.p;
+    G.fsTw = fs.tw.p; G.fsPhase = fs.phase.p; G.fsWindow = fs.window.p;
+    for(int c = 0; c < 4; ++c) G.fsSign[c] = 1.0;
+    return OALGPU_OK;
+}
+int FshifterUpdate(oalgpu_effect *e, float rate, const void *props, const float*)
+{   // FshifterState::update, fshifter.cpp:162-214
+    const auto &p = *static_cast<const oalgpu_fshifter_props*>(props);
+    Fx2Launch &G = e->G;
+    const float step = p.frequency / rate;
+    const uint32_t phaseStep = RoundU(std::min(step, 1.0f) * 65536.0f);
+    for(int c = 0; c < 4; ++c) G.fsPhaseStep[c] = phaseStep;
+    const int32_t dir[2] = {p.left_direction, p.right_direction};
+    for(int side = 0; side < 2; ++side)
+        for(int c = side * 2; c < side * 2 + 2; ++c)
+        {
+            if(dir[side] == OALGPU_FSHIFTER_DOWN) G.fsSign[c] = -1.0;
+            else if(dir[side] == OALGPU_FSHIFTER_UP) G.fsSign[c] = 1.0;
+            else { e->fshifter.phase4[c] = 0; G.fsPhaseStep[c] = 0; }
+        }
+    return OALGPU_OK;
+}
+int FshifterBegin(oalgpu_effect *e, uint32_t&)
+{
+    e->G.fsCount = e->fshifter.hop.count; e->G.fsPos = e->fshifter.hop.pos;
+    for(int c = 0; c < 4; ++c) e->G.fsPhaseIdx[c] = e->fshifter.phase4[c];
+    return OALGPU_OK;
+}
+void FshifterAdvance(oalgpu_effect *e, uint32_t n)
+{   // fshifter.cpp:228-259,330-336
+    AdvanceHop(e->fshifter.hop, 256u, n);
+    for(int c = 0; c < 4; ++c) e->fshifter.phase4[c] = (e->fshifter.phase4[c] + n * e->G.fsPhaseStep[c]) & 65535u;
+}
+
+int PshifterDeviceUpdate(oalgpu_effect *e, FxState&)
+{   // PshifterState::deviceUpdate, pshifter.cpp:128-166: up to second order; pitch 1
+    if(e->numIn > 9) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_create: the pitch shifter works on up to 9 channels (second order)");
+    Fx2Launch &G = e->G; auto &ps = e->pshifter;
+    HIP_TRY(ps.ring.alloc_zero(2 * 9 * 1024));
+    HIP_TRY(ps.phase.alloc_zero(2 * 2 * 513));
+    HIP_TRY(ps.accum.alloc_zero(9 * 1024));
+    HIP_TRY(ps.outFifo.alloc_zero(9 * 128));
+    HIP_TRY(ps.rows.alloc_zero(9 * OALGPU_BUFFER_LINE_SIZE));
+    std::vector<float> tw(2 * 512);
+    for(uint32_t m = 0; m < 512; ++m)
+    {
+        const double a = -2.0 * kPi * double(m) / 1024.0;
+        tw[2 * m] = static_cast<float>(std::cos(a)); tw[2 * m + 1] = static_cast<float>(std::sin(a));
+    }
+    HIP_TRY(ps.tw.alloc(tw.size())); HIP_TRY(ps.tw.upload(tw.data(), tw.size()));
+    if(int rc = UploadHannWindow1024(ps.window)) return rc;
+    G.psAccum = ps.accum.p; G.psOutFifo = ps.outFifo.p; G.psRows = ps.rows.p;
+    G.psTw = ps.tw.p; G.psWindow = ps.window.p;
+    G.psPitchI = 65536u; G.psPitch = 1.0f;
+    return OALGPU_OK;
+}
+int PshifterUpdate(oalgpu_effect *e, float, const void *props, const float*)
+{   // PshifterState::update, pshifter.cpp:168-199
+    const auto &p = *static_cast<const oalgpu_pshifter_props*>(props);
+    const int32_t tune = p.coarse_tune * 100 + p.fine_tune;
+    const float pitch = std::pow(2.0f, float(tune) / 1200.0f);
+    e->G.psPitchI = RoundU(std::min(std::max(pitch, 0.5f), 2.0f) * 65536.0f);
+    e->G.psPitch = float(e->G.psPitchI) * (1.0f / 65536.0f);
+    return OALGPU_OK;
+}
+int PshifterBegin(oalgpu_effect *e, uint32_t&)
+{
+    Fx2Launch &G = e->G; auto &ps = e->pshifter;
+    const uint32_t p = ps.parity;
+    G.psRingIn = ps.ring.p + size_t{p} * 9 * 1024; G.psRingOut = ps.ring.p + size_t{p ^ 1u} * 9 * 1024;
+    G.psPhaseIn = ps.phase.p + size_t{p} * 2 * 513; G.psPhaseOut = ps.phase.p + size_t{p ^ 1u} * 2 * 513;
+    G.psCount = ps.hop.count; G.psPos = ps.hop.pos;
+    return OALGPU_OK;
+}
+void PshifterAdvance(oalgpu_effect *e, uint32_t n) { e->pshifter.parity ^= 1u; AdvanceHop(e->pshifter.hop, 128u, n); }
+
+// What the entry points need to know of a kind: one row per oalgpu_effect_kind, in its order.
+struct KindInfo {
+    const char *subject;                // how update's refusal names the kind
+    bool fx2;                           // LaunchEffect2 (effects2_kernels.hip) instead of LaunchEffect (effects_kernels.hip)
+    bool needProps, needTargets;        // what update may not be called without
+    uint32_t upRows;                    // rows of the up-sampler set_upsampler installs: 4 A-Format, 9 second order, 0 none
+    uint32_t maxWet;                    // the most wet channels it takes
+    // allocation and defaults at create (`fresh`: the FxState an instance of the first five kinds starts from, uploaded afterwards)
+    int (*deviceUpdate)(oalgpu_effect*, FxState &fresh);
+    int (*update)(oalgpu_effect*, float rate, const void *props, const float *gains);   // props to launch constants
+    int (*begin)(oalgpu_effect*, uint32_t &lds);        // the scalars process() reads, into the launch constants; the launch's dynamic LDS
+    void (*advance)(oalgpu_effect*, uint32_t n);        // what process() does to those scalars
+};
+constexpr KindInfo kKinds[OALGPU_EFFECT_PSHIFTER + 1] = {
+    {"equalizer",   false, true,  true,  0, kFxMaxIn, nullptr, EqualizerUpdate, nullptr, nullptr},
+    {"modulator",   false, true,  true,  0, kFxMaxIn, nullptr, ModulatorUpdate, ModulatorBegin, ModulatorAdvance},
+    {"echo",        false, true,  false, 0, kFxMaxIn, EchoDeviceUpdate, EchoUpdate, EchoBegin, EchoAdvance},
+    {"dedicated",   false, false, false, 0, kFxMaxIn, nullptr, DedicatedUpdate, nullptr, nullptr},
+    {"compressor",  false, true,  true,  0, kFxMaxIn, CompressorDeviceUpdate, CompressorUpdate, nullptr, nullptr},
+    {"this effect", true,  true,  true,  4, 4,        ChorusDeviceUpdate, ChorusUpdate, ChorusBegin, ChorusAdvance},
+    {"this effect", true,  true,  true,  4, 4,        DistortionDeviceUpdate, DistortionUpdate, nullptr, nullptr},
+    {"this effect", true,  true,  true,  0, kFxMaxIn, nullptr, AutowahUpdate, nullptr, nullptr},
+    {"this effect", true,  true,  true,  0, kFxMaxIn, nullptr, VmorpherUpdate, VmorpherBegin, VmorpherAdvance},
+    {"this effect", true,  true,  true,  4, 4,        FshifterDeviceUpdate, FshifterUpdate, FshifterBegin, FshifterAdvance},
+    {"this effect", true,  true,  true,  9, 9,        PshifterDeviceUpdate, PshifterUpdate, PshifterBegin, PshifterAdvance},
+};
+
+// mChans[c].mTargetChannel / mTargetGain of the first `chans` wet channels (no `gains`: the up-sampler's rows hold them)
+template<typename Launch>
+void SetTargets(Launch &L, uint32_t chans, const uint32_t *target_channels, const float *gains)
+{
+    for(uint32_t ch = 0; ch < kFxMaxIn; ++ch) { L.target[ch] = OALGPU_INVALID_CHANNEL; L.tgtGain[ch] = 0.0f; }
+    for(uint32_t ch = 0; ch < chans; ++ch) { L.target[ch] = target_channels[ch]; if(gains) L.tgtGain[ch] = gains[ch]; }
 }
 
 } // namespace
@@ -273,119 +474,31 @@ int oalgpu_effect_create(int device, int math_mode, int kind, uint32_t sample_ra
         return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_create: bad arguments");
     *out = nullptr;
     if(int rc = UseDevice(device)) return rc;
+    const KindInfo &K = kKinds[kind];
     auto e = std::make_unique<oalgpu_effect>();
-    e->device = device; e->kind = kind; e->exact = math_mode == OALGPU_MATH_EXACT;
-    e->sampleRate = sample_rate; e->numIn = num_in_channels; e->nlines = num_out_lines;
-    HIP_TRY(e->st.alloc(1)); HIP_TRY(e->st.zero());
-    HIP_TRY(e->tgtGains.alloc(2 * OALGPU_MAX_OUTPUT_CHANNELS)); HIP_TRY(e->tgtGains.zero());
+    e->device = device; e->kind = kind; e->sampleRate = sample_rate; e->numIn = num_in_channels; e->nlines = num_out_lines;
+    HIP_TRY(e->st.alloc_zero(1));
+    HIP_TRY(e->tgtGains.alloc_zero(2 * OALGPU_MAX_OUTPUT_CHANNELS));
     HIP_TRY(e->hostIn.alloc(size_t{num_in_channels} * OALGPU_BUFFER_LINE_SIZE));
     HIP_TRY(e->hostOut.alloc(size_t{num_out_lines} * OALGPU_BUFFER_LINE_SIZE));
     FxLaunch &F = e->F;
-    F.kind = kind; F.exact = e->exact ? 1 : 0; F.numIn = num_in_channels; F.nlines = num_out_lines;
+    F.kind = kind; F.exact = math_mode == OALGPU_MATH_EXACT ? 1 : 0; F.numIn = num_in_channels; F.nlines = num_out_lines;
     F.st = e->st.p; F.tgtGains = e->tgtGains.p;
-    for(uint32_t c = 0; c < kFxMaxIn; ++c) { F.target[c] = OALGPU_INVALID_CHANNEL; F.tgtGain[c] = 0.0f; }
+    SetTargets(F, 0, nullptr, nullptr);
     F.modRange = 1; F.modWave = 0;
-    if(kind == OALGPU_EFFECT_ECHO)
-    {   // EchoState::deviceUpdate, echo.cpp:77-91: EchoMaxDelay 0.207 s + EchoMaxLRDelay 0.404 s, next power of two
-        const float f = float(sample_rate);
-        const uint32_t len = NextPow2(uint32_t(0.207f * f + 0.5f) + uint32_t(0.404f * f + 0.5f));
-        HIP_TRY(e->delay.alloc(len)); HIP_TRY(e->delay.zero());
-        F.delay = e->delay.p; F.delayMask = len - 1u;
-    }
-    if(kind == OALGPU_EFFECT_COMPRESSOR)
-    {   // CompressorState::deviceUpdate, compressor.cpp:87-101: 100 ms from 0.5 to 2, 200 ms back; mEnvFollower = 1
-        F.attackMult = std::pow(2.0f / 0.5f, 1.0f / (float(sample_rate) * 0.1f));
-        F.releaseMult = std::pow(0.5f / 2.0f, 1.0f / (float(sample_rate) * 0.2f));
-        const float one = 1.0f;
-        HIP_TRY(hipMemcpy(reinterpret_cast<char*>(e->st.p) + offsetof(FxState, env), &one, sizeof(one), hipMemcpyHostToDevice));
-    }
-    if(IsFx2(kind))
+    if(K.fx2)
     {
-        const float f = float(sample_rate);
-        HIP_TRY(e->st2.alloc(1)); HIP_TRY(e->st2.zero());
-        HIP_TRY(e->upTgt.alloc(9 * 32)); HIP_TRY(e->upTgt.zero());
+        HIP_TRY(e->st2.alloc_zero(1));
+        HIP_TRY(e->upTgt.alloc_zero(9 * 32));
         Fx2Launch &G = e->G;
         G.kind = kind; G.numIn = num_in_channels; G.nlines = num_out_lines; G.st = e->st2.p; G.upTgt = e->upTgt.p;
-        for(uint32_t c = 0; c < kFxMaxIn; ++c) { G.target[c] = OALGPU_INVALID_CHANNEL; G.tgtGain[c] = 0.0f; }
-        G.hfScale[0] = G.hfScale[1] = 1.0f;
-        G.lfoRange = 1;
-        if(kind == OALGPU_EFFECT_CHORUS)
-        {   // ChorusState::deviceUpdate, chorus.cpp:129-163: four lines of NextPowerOf2(2 * max(ChorusMaxDelay, FlangerMaxDelay) * rate + 1)
-            const uint32_t len = NextPow2(TruncU(0.016f * 2.0f * f) + 1u);
-            HIP_TRY(e->delay.alloc(size_t{len} * 4)); HIP_TRY(e->delay.zero());
-            HIP_TRY(e->cubic.alloc(kFineCubicSteps * 2 + 1));
-            HIP_TRY(e->cubic.upload(GetFineCubicFilter(), kFineCubicSteps * 2 + 1));
-            G.delay = e->delay.p; G.delayMask = len - 1u; G.cubic = e->cubic.p;
-        }
-        if(kind == OALGPU_EFFECT_DISTORTION)
-        {
-            BiquadState ident{}; ident.b0 = 1.0f;
-            BiquadState eight[8]; for(auto &b : eight) b = ident;
-            if(int rc = UploadAt(e->st2.p, offsetof(Fx2State, lp), eight, 8)) return rc;
-        }
-        if(kind == OALGPU_EFFECT_AUTOWAH)
-        {   // AutowahState::deviceUpdate, autowah.cpp:86-98
-            G.attackRate = 1.0f; G.releaseRate = 1.0f; G.resonanceGain = 10.0f; G.peakGain = 4.5f;
-            G.freqMinNorm = 4.5e-4f; G.bandwidthNorm = 0.05f;
-        }
-        if(kind == OALGPU_EFFECT_VMORPHER)
-            for(int k = 0; k < 8; ++k) { G.vmG[k] = 0.0f; G.vmGain[k] = 1.0f; }       // FormantFilter{}
-        if(kind == OALGPU_EFFECT_FSHIFTER)
-        {   // FshifterState::deviceUpdate, fshifter.cpp:133-160; the Hann window of common/hann_window.hpp
-            HIP_TRY(e->fsIn.alloc(4 * 1024)); HIP_TRY(e->fsIn.zero());
-            HIP_TRY(e->fsOutFifo.alloc(4 * 256)); HIP_TRY(e->fsOutFifo.zero());
-            HIP_TRY(e->fsAccum.alloc(4 * 1024)); HIP_TRY(e->fsAccum.zero());
-            HIP_TRY(e->fsOutdata.alloc(4 * OALGPU_BUFFER_LINE_SIZE)); HIP_TRY(e->fsOutdata.zero());
-            std::vector<FsPair> tw; BuildTwiddles(tw);
-            HIP_TRY(e->fsTw.alloc(tw.size()));
-            HIP_TRY(e->fsTw.upload(tw.data(), tw.size()));
-            // cos / sin of phase_idx * (pi*2 / MixerFracOne), fshifter.cpp:323-326: one entry per phase index
-            std::vector<FsPair> ph(65536);
-            for(uint32_t i = 0; i < 65536; ++i)
-            {
-                const double phase = i * (3.14159265358979323846 * 2.0 / 65536.0);
-                ph[i] = FsPair{std::cos(phase), std::sin(phase)};
-            }
-            HIP_TRY(e->fsPhase.alloc(ph.size()));
-            HIP_TRY(e->fsPhase.upload(ph.data(), ph.size()));
-            const std::vector<float> win = HannWindow1024();
-            HIP_TRY(e->window.alloc(win.size()));
-            HIP_TRY(e->window.upload(win.data(), win.size()));
-            G.fsIn = e->fsIn.p; G.fsOutFifo = e->fsOutFifo.p; G.fsAccum = e->fsAccum.p; G.fsOutdata = e->fsOutdata.p;
-            G.fsTw = e->fsTw.p; G.fsPhase = e->fsPhase.p; G.fsWindow = e->window.p;
-            for(int c = 0; c < 4; ++c) G.fsSign[c] = 1.0;
-        }
-        if(kind == OALGPU_EFFECT_PSHIFTER)
-        {   // PshifterState::deviceUpdate, pshifter.cpp:128-166: up to second order; pitch 1
-            if(num_in_channels > 9) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_create: the pitch shifter works on up to 9 channels (second order)");
-            HIP_TRY(e->psRing.alloc(2 * 9 * 1024)); HIP_TRY(e->psRing.zero());
-            HIP_TRY(e->psPhase.alloc(2 * 2 * 513)); HIP_TRY(e->psPhase.zero());
-            HIP_TRY(e->psAccum.alloc(9 * 1024)); HIP_TRY(e->psAccum.zero());
-            HIP_TRY(e->psOutFifo.alloc(9 * 128)); HIP_TRY(e->psOutFifo.zero());
-            HIP_TRY(e->psRows.alloc(9 * OALGPU_BUFFER_LINE_SIZE)); HIP_TRY(e->psRows.zero());
-            std::vector<float> tw(2 * 512);
-            for(uint32_t m = 0; m < 512; ++m)
-            {
-                const double a = -2.0 * 3.14159265358979323846 * double(m) / 1024.0;
-                tw[2 * m] = static_cast<float>(std::cos(a)); tw[2 * m + 1] = static_cast<float>(std::sin(a));
-            }
-            HIP_TRY(e->psTw.alloc(tw.size())); HIP_TRY(e->psTw.upload(tw.data(), tw.size()));
-            const std::vector<float> win = HannWindow1024();
-            HIP_TRY(e->window.alloc(win.size())); HIP_TRY(e->window.upload(win.data(), win.size()));
-            G.psAccum = e->psAccum.p; G.psOutFifo = e->psOutFifo.p; G.psRows = e->psRows.p;
-            G.psTw = e->psTw.p; G.psWindow = e->window.p;
-            G.psPitchI = 65536u; G.psPitch = 1.0f;
-        }
-        *out = e.release();
-        return OALGPU_OK;
+        SetTargets(G, 0, nullptr, nullptr);
+        G.hfScale[0] = G.hfScale[1] = 1.0f; G.lfoRange = 1;
     }
-    // a BiquadFilter starts as the identity (mB0 = 1)
-    for(uint32_t c = 0; c < kFxMaxIn; ++c)
-        for(uint32_t k = 0; k < 4; ++k)
-        {
-            const float ident[5] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            if(int rc = UploadBiquad(e.get(), c, k, ident)) return rc;
-        }
+    FxState fresh{};                     // a BiquadFilter starts as the identity (mB0 = 1)
+    for(auto &chan : fresh.bq) for(BiquadState &b : chan) b.b0 = 1.0f;
+    if(K.deviceUpdate) { if(int rc = K.deviceUpdate(e.get(), fresh)) return rc; }
+    if(!K.fx2) HIP_TRY(e->st.upload(&fresh, 1));
     *out = e.release();
     return OALGPU_OK;
 }
@@ -403,74 +516,25 @@ int oalgpu_effect_update(oalgpu_effect *e, const void *props, const uint32_t *ta
     if(!e || !gains) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: null argument");
     if(int rc = UseDevice(e->device)) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    const float rate = float(e->sampleRate);
-    if(IsFx2(e->kind)) return UpdateFx2(e, props, target_channels, gains);
-    FxLaunch &F = e->F;
-    switch(e->kind)
+    const KindInfo &K = kKinds[e->kind];
+    if((K.needProps && !props) || (K.needTargets && !target_channels))
+        return Fail(OALGPU_ERR_INVALID, std::string("oalgpu_effect_update: ") + K.subject + " needs props" + (K.needTargets ? " and targets" : ""));
+    if(int rc = K.update(e, float(e->sampleRate), props, gains)) return rc;
+    if(K.needTargets)
     {
-    case OALGPU_EFFECT_EQUALIZER:
-        {   // EqualizerState::update, equalizer.cpp:115-165
-            if(!props || !target_channels) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: equalizer needs props and targets");
-            const auto &p = *static_cast<const oalgpu_equalizer_props*>(props);
-            float c[4][5];
-            DesignBiquadFromSlope(OALGPU_BIQUAD_LOWSHELF, p.low_cutoff / rate, std::sqrt(p.low_gain), 0.75f, c[0]);
-            DesignBiquadFromBandwidth(OALGPU_BIQUAD_PEAKING, p.mid1_center / rate, std::sqrt(p.mid1_gain), p.mid1_width, c[1]);
-            DesignBiquadFromBandwidth(OALGPU_BIQUAD_PEAKING, p.mid2_center / rate, std::sqrt(p.mid2_gain), p.mid2_width, c[2]);
-            DesignBiquadFromSlope(OALGPU_BIQUAD_HIGHSHELF, p.high_cutoff / rate, std::sqrt(p.high_gain), 0.75f, c[3]);
-            for(uint32_t ch = 0; ch < e->numIn; ++ch)
-                for(uint32_t k = 0; k < 4; ++k)
-                    if(int rc = UploadBiquad(e, ch, k, c[k])) return rc;
+        const bool up = K.upRows && e->G.upsample;
+        if(up)
+        {   // UpsampleParams::mTargetGains = ComputePanGains(target.Main, AmbiScale::FirstOrderUp[ch] (pitch shifter: SecondOrderUp[ch]),
+            // gain): gains[4 or 9][num_out_lines]
+            std::vector<float> rows(9 * 32, 0.0f);
+            for(uint32_t ch = 0; ch < K.upRows; ++ch)
+                for(uint32_t l = 0; l < e->nlines; ++l) rows[ch * 32 + l] = gains[size_t{ch} * e->nlines + l];
+            HIP_TRY(e->upTgt.upload(rows.data(), rows.size()));
         }
-        break;
-    case OALGPU_EFFECT_MODULATOR:
-        {   // ModulatorState::update, modulator.cpp:103-163
-            if(!props || !target_channels) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: modulator needs props and targets");
-            const auto &p = *static_cast<const oalgpu_modulator_props*>(props);
-            const float perCycle = p.frequency > 0.0f ? rate / p.frequency + 0.5f : 1.0f;
-            const uint32_t range = uint32_t(std::min(std::max(perCycle, 1.0f), rate));
-            e->modIndex = uint32_t(uint64_t{e->modIndex} * range / e->modRange);
-            e->modRange = range;
-            F.modScale = 0.0f; F.modWave = 0;
-            if(e->modRange == 1) {}
-            else if(p.waveform == OALGPU_MODULATOR_SINUSOID) { F.modScale = 3.14159265358979323846f * 2.0f / float(e->modRange); F.modWave = 1; }
-            else if(p.waveform == OALGPU_MODULATOR_SAWTOOTH) { F.modScale = 2.0f / float(e->modRange - 1u); F.modWave = 2; }
-            else
-            {
-                e->modRange = (e->modRange + 1u) & ~1u;
-                F.modScale = 1.0f / float(e->modRange - 1u); F.modWave = 3;
-            }
-            const float f0norm = std::min(std::max(p.high_pass_cutoff / rate, 1.0f / 512.0f), 0.49f);
-            float c[5];
-            DesignBiquadFromBandwidth(OALGPU_BIQUAD_HIGHPASS, f0norm, 1.0f, 0.75f, c);
-            for(uint32_t ch = 0; ch < e->numIn; ++ch)
-                if(int rc = UploadBiquad(e, ch, 0, c)) return rc;
-        }
-        break;
-    case OALGPU_EFFECT_COMPRESSOR:
-        if(!props || !target_channels) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: compressor needs props and targets");
-        F.compOn = static_cast<const oalgpu_compressor_props*>(props)->on_off ? 1 : 0;
-        break;
-    case OALGPU_EFFECT_ECHO:
-        {   // EchoState::update, echo.cpp:93-117 (the two taps' panned gains come from the caller)
-            if(!props) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: echo needs props");
-            const auto &p = *static_cast<const oalgpu_echo_props*>(props);
-            F.tap[0] = std::max(uint32_t(std::round(p.delay * rate)), 1u);
-            F.tap[1] = uint32_t(std::round(p.lr_delay * rate)) + F.tap[0];
-            if(F.tap[1] > F.delayMask) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_update: echo delays beyond AL_ECHO_MAX_DELAY + AL_ECHO_MAX_LRDELAY");
-            const float gainhf = std::max(1.0f - p.damping, 0.0625f);
-            float c[5];
-            DesignBiquadFromSlope(OALGPU_BIQUAD_HIGHSHELF, 5000.0f / rate, gainhf, 1.0f, c);
-            if(int rc = UploadBiquad(e, 0, 0, c)) return rc;
-            F.feedGain = p.feedback;
-            HIP_TRY(e->tgtGains.upload(gains, size_t{2} * e->nlines));
-        }
-        break;
-    default:    // DedicatedState::update, dedicated.cpp:66-100: the gains of the target line(s), resolved by the caller
-        HIP_TRY(e->tgtGains.upload(gains, e->nlines));
-        break;
+        const uint32_t chans = std::min(e->numIn, K.maxWet);
+        if(K.fx2) SetTargets(e->G, chans, target_channels, up ? nullptr : gains);
+        else SetTargets(e->F, chans, target_channels, gains);
     }
-    if(e->kind == OALGPU_EFFECT_EQUALIZER || e->kind == OALGPU_EFFECT_MODULATOR || e->kind == OALGPU_EFFECT_COMPRESSOR)
-        for(uint32_t ch = 0; ch < e->numIn; ++ch) { F.target[ch] = target_channels[ch]; F.tgtGain[ch] = gains[ch]; }
     e->updated = true;
     return OALGPU_OK;
 }
@@ -479,8 +543,7 @@ int oalgpu_effect_update(oalgpu_effect *e, const void *props, const uint32_t *ta
 int oalgpu_effect_set_upsampler(oalgpu_effect *e, const float order_scales[2], float xover_norm)
 {
     if(!e) return Fail(OALGPU_ERR_INVALID, "null argument");
-    if(!(e->kind == OALGPU_EFFECT_CHORUS || e->kind == OALGPU_EFFECT_DISTORTION || e->kind == OALGPU_EFFECT_FSHIFTER
-        || e->kind == OALGPU_EFFECT_PSHIFTER))
+    if(!kKinds[e->kind].upRows)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_set_upsampler: only the chorus, the distortion and the frequency / pitch shifters up-sample");
     if(e->nlines > 32) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_set_upsampler: at most 32 output lines");
     if(int rc = UseDevice(e->device)) return rc;
@@ -501,86 +564,20 @@ int oalgpu_effect_set_upsampler(oalgpu_effect *e, const float order_scales[2], f
 
 } // extern "C"
 
-namespace {
-int ProcessFx2(oalgpu_effect *e, hipStream_t stream, const float *wet_in_dev, float *out_lines_dev, uint32_t n)
-{
-    Fx2Launch G = e->G;
-    G.wetIn = wet_in_dev; G.outLines = out_lines_dev; G.n = n;
-    uint32_t lds = 0;
-    if(e->kind == OALGPU_EFFECT_CHORUS)
-    {
-        G.offset = e->chOffset;
-        G.lfoStart[0] = e->lfoOffset;
-        G.lfoStart[1] = (e->lfoOffset + e->lfoDisp) % e->lfoRange;
-        lds = (6u * OALGPU_BUFFER_LINE_SIZE + G.chHist + OALGPU_BUFFER_LINE_SIZE) * sizeof(float);
-        if(lds > 65536u) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_process: chorus delay too long for the workgroup's LDS");
-    }
-    if(e->kind == OALGPU_EFFECT_VMORPHER) G.vmIndex = e->vmIndex;
-    if(e->kind == OALGPU_EFFECT_FSHIFTER)
-    {
-        G.fsCount = e->fsCount; G.fsPos = e->fsPos;
-        for(int c = 0; c < 4; ++c) G.fsPhaseIdx[c] = e->fsPhase4[c];
-    }
-    if(e->kind == OALGPU_EFFECT_PSHIFTER)
-    {
-        const uint32_t p = e->psParity;
-        G.psRingIn = e->psRing.p + size_t{p} * 9 * 1024; G.psRingOut = e->psRing.p + size_t{p ^ 1u} * 9 * 1024;
-        G.psPhaseIn = e->psPhase.p + size_t{p} * 2 * 513; G.psPhaseOut = e->psPhase.p + size_t{p ^ 1u} * 2 * 513;
-        G.psCount = e->psCount; G.psPos = e->psPos;
-    }
-    LaunchEffect2(stream, G, lds);
-    HIP_TRY(hipGetLastError());
-    // the scalars process() moves on (chorus.cpp:283,391; vmorpher.cpp:293-294; fshifter.cpp:228-259,330-336)
-    if(e->kind == OALGPU_EFFECT_CHORUS)
-    {
-        e->chOffset += n;
-        e->lfoOffset = (e->lfoOffset + n) % e->lfoRange;
-    }
-    if(e->kind == OALGPU_EFFECT_PSHIFTER)
-    {
-        e->psParity ^= 1u;
-        for(uint32_t base = 0; base < n;)
-        {
-            const uint32_t todo = std::min(128u - e->psCount, n - base);
-            e->psCount += todo; base += todo;
-            if(e->psCount < 128u) break;
-            e->psCount = 0; e->psPos = (e->psPos + 128u) & 1023u;
-        }
-    }
-    if(e->kind == OALGPU_EFFECT_VMORPHER)
-        for(uint32_t base = 0; base < n; base += 256u)
-            e->vmIndex = (e->vmIndex + G.vmStep * std::min(256u, n - base)) & 0xffffffu;
-    if(e->kind == OALGPU_EFFECT_FSHIFTER)
-    {
-        for(uint32_t base = 0; base < n;)
-        {
-            const uint32_t todo = std::min(256u - e->fsCount, n - base);
-            e->fsCount += todo; base += todo;
-            if(e->fsCount < 256u) break;
-            e->fsCount = 0; e->fsPos = (e->fsPos + 256u) & 1023u;
-        }
-        for(int c = 0; c < 4; ++c) e->fsPhase4[c] = (e->fsPhase4[c] + n * G.fsPhaseStep[c]) & 65535u;
-    }
-    return OALGPU_OK;
-}
-} // namespace
-
 int oalgpu_effect_process_device(oalgpu_effect *e, void *hip_stream, const float *wet_in_dev, float *out_lines_dev, uint32_t n)
 {
     if(!e || !wet_in_dev || !out_lines_dev || n == 0 || n > OALGPU_BUFFER_LINE_SIZE)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_process: bad arguments");
     if(!e->updated) return Fail(OALGPU_ERR_INVALID, "oalgpu_effect_process: no update() yet");
     if(int rc = UseDevice(e->device)) return rc;
-    if(IsFx2(e->kind)) return ProcessFx2(e, static_cast<hipStream_t>(hip_stream), wet_in_dev, out_lines_dev, n);
-    FxLaunch F = e->F;
-    F.wetIn = wet_in_dev; F.outLines = out_lines_dev; F.n = n;
-    F.modIndex = e->modIndex; F.modRange = e->modRange;
-    F.offset = e->echoOffset;
-    LaunchEffect(static_cast<hipStream_t>(hip_stream), F);
+    const KindInfo &K = kKinds[e->kind];
+    uint32_t lds = 0;
+    if(K.begin) { if(int rc = K.begin(e, lds)) return rc; }
+    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if(K.fx2) { Fx2Launch G = e->G; G.wetIn = wet_in_dev; G.outLines = out_lines_dev; G.n = n; LaunchEffect2(stream, G, lds); }
+    else { FxLaunch F = e->F; F.wetIn = wet_in_dev; F.outLines = out_lines_dev; F.n = n; LaunchEffect(stream, F); }
     HIP_TRY(hipGetLastError());
-    // what process() does to the scalars (modulator.cpp:176-189, echo.cpp:127-157)
-    if(e->kind == OALGPU_EFFECT_MODULATOR && e->modRange > 1) e->modIndex = (e->modIndex + n) % e->modRange;
-    if(e->kind == OALGPU_EFFECT_ECHO) e->echoOffset = (e->echoOffset + n) & F.delayMask;
+    if(K.advance) K.advance(e, n);
     return OALGPU_OK;
 }
 

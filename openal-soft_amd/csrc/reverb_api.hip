@@ -67,12 +67,12 @@ int oalgpu_reverb_create(int device, uint32_t sample_rate, uint32_t num_out_line
     if(sample_rate > kRvMaxSampleRate)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_reverb_create: sample rates above 48 kHz are not supported");
     if(int rc = UseDevice(device)) return rc;
-    HIP_TRY(r->samples.alloc(r->total)); HIP_TRY(r->samples.zero());
-    HIP_TRY(r->scratch.alloc(size_t{2} * 2 * 4 * OALGPU_BUFFER_LINE_SIZE)); HIP_TRY(r->scratch.zero());
+    HIP_TRY(r->samples.alloc_zero(r->total));
+    HIP_TRY(r->scratch.alloc_zero(size_t{2} * 2 * 4 * OALGPU_BUFFER_LINE_SIZE));
     HIP_TRY(r->cubic.alloc(kFineCubicSteps * 2 + 1));
     HIP_TRY(r->cubic.upload(GetFineCubicFilter(), kFineCubicSteps * 2 + 1));
     HIP_TRY(r->pipe.alloc(2)); HIP_TRY(r->pipe.upload(r->host.params.pipe, 2));
-    HIP_TRY(r->state.alloc(2)); HIP_TRY(r->state.zero());
+    HIP_TRY(r->state.alloc_zero(2));
     HIP_TRY(r->hostIn.alloc(size_t{4} * OALGPU_BUFFER_LINE_SIZE));
     HIP_TRY(r->hostOut.alloc(size_t{num_out_lines} * OALGPU_BUFFER_LINE_SIZE));
     r->dirty[0] = r->dirty[1] = false;
@@ -274,7 +274,7 @@ int oalgpu_reverb_debug_enable_phase_times(oalgpu_reverb *r)
 {
     if(!r || r->device < 0) return Fail(OALGPU_ERR_INVALID, "oalgpu_reverb_debug_enable_phase_times: needs a device instance");
     HIP_TRY(hipStreamSynchronize(r->stream));
-    HIP_TRY(r->stamps.alloc(4 * 8 * 8)); HIP_TRY(r->stamps.zero());
+    HIP_TRY(r->stamps.alloc_zero(4 * 8 * 8));
     r->L.stamps = r->stamps.p;
     return OALGPU_OK;
 }
