@@ -252,20 +252,16 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     L.hrirs = nullptr;
     for(uint32_t &n : L.chansPerOrder) n = 0;
     L.accLines = 0;
-    L.sliceLines = 0;
     L.wave16 = 0;                           // (decided when the HRTF data set is known: InstallHrtfData)
     L.rows8 = 0; L.rowsVpg = 0;
     if(c->useWave && !(desc->flags & OALGPU_CTX_STREAM_ROWS))
     {
         L.accLines = WaveKernelAccLines(L);
-        // dry lines AND sends, or more lines than the wavefront-per-voice kernel holds in registers: stream rows, or -- opt-in,
-        // OALGPU_CTX_SLICE_LINES -- a wavefront per 256-frame slice (voice_slice.hip: a third of the traffic, twice the time); the
-        // measurement variants (OALGPU_CTX_PROFILE) exist for the stream-row kernel only
-        if(!L.accLines && (desc->flags & OALGPU_CTX_SLICE_LINES) && !(desc->flags & OALGPU_CTX_PROFILE)) L.sliceLines = SliceKernelLines(L);
-        // ... by default the rows stay in LDS: a wavefront per voice produces, a wavefront per 128-frame slice of every line
+        // dry lines AND sends, or more lines than the wavefront-per-voice kernel holds in registers: by default
+        // the rows stay in LDS -- a wavefront per voice produces, a wavefront per 128-frame slice of every line
         // consumes, the round's filters are jobs dealt to all eight wavefronts (voice_rows.hip); one workgroup per compute unit
         // (SetRowsGroups below).  OALGPU_CTX_STREAM_ROWS keeps the rows in HBM (above); OALGPU_CTX_ROW_SLICES asks for this form by name.
-        if(!L.accLines && !L.sliceLines && RowsKernelApplies(L))
+        if(!L.accLines && RowsKernelApplies(L))
             L.rows8 = 1;
     }
     if(c->useWave && (!L.hrtf || L.numSends))
@@ -274,11 +270,11 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
         L.lineStride = L.mixLines <= 8 ? 8u : (L.mixLines <= 16 ? 16u : 32u);
         L.streamsPerVoice = 2u + L.numSends;
     }
-    if(c->useWave && (!L.hrtf || L.numSends) && !L.accLines && !L.sliceLines && !L.rows8) { if(int rc = AllocStreamRows(c.get())) return rc; }
+    if(c->useWave && (!L.hrtf || L.numSends) && !L.accLines && !L.rows8) { if(int rc = AllocStreamRows(c.get())) return rc; }
     const size_t groups = c->groupsAllocated;
     HIP_TRY(c->partLines.alloc(groups * L.mixLines * kLine)); L.partLines = c->partLines.p;
     // the two-stream pipeline of oalgpu_mix_update alternates between two sets of partial buses
-    HIP_TRY(c->partLines2.alloc(c->useWave && (L.streams || L.accLines || L.sliceLines || L.rows8) ? groups * L.mixLines * kLine : 0));
+    HIP_TRY(c->partLines2.alloc(c->useWave && (L.streams || L.accLines || L.rows8) ? groups * L.mixLines * kLine : 0));
     c->partLinesBuf[0] = c->partLines.p; c->partLinesBuf[1] = c->partLines2.p;
     HIP_TRY(c->partHrtf.alloc(L.hrtf ? groups * (kLine + kHrirLen) * 2 : 0)); L.partHrtf = c->partHrtf.p;
     HIP_TRY(c->partHrtf2.alloc(c->useWave && L.hrtf ? groups * (kLine + kHrirLen) * 2 : 0));
@@ -863,7 +859,7 @@ int oalgpu_mix_voices_overlapped(oalgpu_context *c, uint32_t samples_to_do)
     const uint32_t p = c->parity;
     DeviceLayout L = c->L;
     L.partHrtf = c->partHrtfBuf[p];
-    if(L.streams || L.accLines || L.sliceLines || L.rows8) L.partLines = c->partLinesBuf[p];
+    if(L.streams || L.accLines || L.rows8) L.partLines = c->partLinesBuf[p];
     // main stream: this update's voices; its partial-bus buffer was last read by the reduction
     // of two updates ago
     // (almost always long done: then no barrier packet goes into the main queue in front of the voice kernel)

@@ -10,7 +10,7 @@ static uint32_t ChooseWave16(const oalgpu_context *c, const DeviceLayout &T)
     // the HRTF path keeps its four wavefronts per SIMD; OALGPU_CTX_WAVE_PAIRS keeps the wet lines in the registers of the
     // two-voices-per-wavefront kernel, OALGPU_CTX_STREAM_ROWS its stream rows)
     const bool want16 = !(c->desc.flags & OALGPU_CTX_WAVE_PAIRS) && Wave16Applies(T)
-        && (T.numSends == 0 || !(c->desc.flags & (OALGPU_CTX_STREAM_ROWS | OALGPU_CTX_PROFILE | OALGPU_CTX_SLICE_LINES)));
+        && (T.numSends == 0 || !(c->desc.flags & (OALGPU_CTX_STREAM_ROWS | OALGPU_CTX_PROFILE)));
     if(!want16) return 0u;
     if(!c->desc.voices_per_group) return Wave16WavesFor(T.numVoices, DeviceComputeUnits(c->desc.device));
     for(uint32_t w : {4u, 8u, 16u})

@@ -51,8 +51,10 @@ int oalgpu_read_output_async(oalgpu_context *c, uint32_t *ticket)
     hipStream_t s = (c->useWave && c->ownStream && !c->serialOnly && c->postStream) ? c->postStream : c->stream;
     HIP_TRY(hipMemcpyAsync(c->outHost[slot], RealOut(c), floats * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(c->outDone[slot], s));
-    // (a resident context's next reduction runs on a stream of its own and rewrites these lines: it has to wait for the copy)
-    if(c->res.running) c->res.copyPending = c->outDone[slot];
+    // (a resident context's next reduction runs on a stream of its own and rewrites these lines: it has to wait for the copy --
+    // also when the kernel is parked, as by this call's first allocation of the slots: the next launch's reduction waits for the
+    // post stream's last event, which lies in front of this copy)
+    if(c->res.enabled && !c->res.failed) c->res.copyPending = c->outDone[slot];
     *ticket = c->outNext++;
     return OALGPU_OK;
 }

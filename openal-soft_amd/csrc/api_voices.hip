@@ -273,7 +273,6 @@ int oalgpu_context_set_nfc(oalgpu_context *c, float w1, const uint32_t channels_
     if(c->useWave)
     {   // the wavefront kernel: every order adds one stream row per voice (near-field contexts mix through stream rows)
         L.accLines = 0;
-        L.sliceLines = 0;
         if(L.rows8)
         {   // (back to the wavefront-per-voice grid: the rows kernel has no near-field rows)
             L.rows8 = 0; L.rowsVpg = 0;

@@ -7,10 +7,10 @@
 //      -> DoFilters, direct path and per send              voice.cpp:255-267, :966-983
 //      -> MixSamples onto the dry lines and the slots' wet lines   voice.cpp:934-984, core/mixer/mixer_c.cpp:150-259
 //
-// The two forms this replaces both pay for 21 mix lines.  voice_wave.hip's stream rows: a wavefront per voice leaves a 4 KB row
-// per mixed signal in HBM and the workgroup's tail reads them back -- 6.5 x the algorithmic bytes.  voice_slice.hip: a wavefront
-// per 256-frame slice keeps the lines in registers and never writes a row -- and resamples, filters and resolves every voice
-// four times (instruction-bound: twice the time).  Here the cut is along BOTH axes:
+// The two forms this replaced both paid for 21 mix lines.  voice_wave.hip's stream rows: a wavefront per voice leaves a 4 KB row
+// per mixed signal in HBM and the workgroup's tail reads them back -- 6.5 x the algorithmic bytes.  The retired wavefront per
+// 256-frame slice kept the lines in registers and never wrote a row -- and resampled, filtered and resolved
+// every voice four times (instruction-bound: twice the time).  Here the cut is along BOTH axes:
 //   * PRODUCE: a wavefront owns a voice -- request, resampler (the register form of voice_wave16.hip: outputs lane + 64 j in 16
 //     registers) -- once per voice; what MixSamples would read goes into a 4 KB row slot in LDS together with the resolved
 //     gains of the lines it feeds (line = lane);

@@ -1690,7 +1690,6 @@ const char *WaveKernelName(const DeviceLayout &L)
 {
     if(L.wave16) return Wave16KernelName(L);
     if(L.rows8) return RowsKernelName();
-    if(L.sliceLines) return SliceKernelName();
     const bool sends = L.numSends != 0;
     if(L.accLines)
         return !L.hrtf ? "VoiceWaveKernel<17, 64, 1, false, false, false, DeviceLayout, 6>" : "VoiceWaveKernel<17, 64, 0, true, true, false, DeviceLayout, 4>";
@@ -1710,8 +1709,8 @@ uint32_t WaveKernelGroups(const DeviceLayout &L)
 // prof: null in production; the measurement variants exist for the HRTF kernels without sends only
 // evStart / evStop (both or neither): HIP events bound to the DISPATCH (hipExtLaunchKernel) -- the kernel's own start and end,
 // what rocprofv3's kernel trace reports, without the command-processor time an event recorded around the launch includes
-// the kernels whose wavefronts install a parameter block behind their voices: every VoiceWaveKernel (voice_slice.hip has no such epilogue)
-bool WaveKernelAppliesRecords(const DeviceLayout &L) { return L.sliceLines == 0 && !(L.wave16 && L.numSends); }      // (every VoiceWaveKernel; not the slice kernel, not voice_wave16.hip's with sends)
+// the kernels whose wavefronts install a parameter block behind their voices
+bool WaveKernelAppliesRecords(const DeviceLayout &L) { return !(L.wave16 && L.numSends); }      // (every VoiceWaveKernel; not voice_wave16.hip's with sends)
 
 hipError_t LaunchStreamRowsMix(hipStream_t s, const DeviceLayout &L, uint32_t samplesToDo, uint32_t vpg, hipEvent_t evStop)
 {
@@ -1727,7 +1726,6 @@ hipError_t LaunchVoiceWave(hipStream_t s, const DeviceLayout &L, uint32_t sample
 {
     if(L.wave16) return LaunchVoiceWave16(s, L, samplesToDo, prof, evStart, evStop, nextRecs, nextMap, L.hrtf ? nextRows : nullptr);   // (voice_wave16.hip)
     if(L.rows8) return LaunchVoiceRows(s, L, samplesToDo, prof, evStart, evStop, nextRecs, nextMap);      // (voice_rows.hip)
-    if(L.sliceLines) return LaunchVoiceSlice(s, L, samplesToDo, evStart, evStop);       // (voice_slice.hip)
     const NextBlock next{nextRecs, nextMap, L.hrtf ? nextRows : nullptr, ResidentArgs{}};
     const uint32_t groups = WaveKernelGroups(L);
     const bool sends = L.numSends != 0;

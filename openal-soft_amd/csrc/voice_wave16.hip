@@ -1023,7 +1023,7 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
 // FAST HRTF contexts on the matrix-pipe FIR, without sends or -- `sends` -- with them (their rows leave as stream rows, see W16Sends)
 bool Wave16Applies(const DeviceLayout &L)
 {
-    if(!(L.hrtf && L.firMfma && L.irStride >= 8 && L.irStride <= 64 && L.sliceLines == 0 && L.nfc == nullptr)) return false;
+    if(!(L.hrtf && L.firMfma && L.irStride >= 8 && L.irStride <= 64 && L.nfc == nullptr)) return false;
     if(L.numSends == 0) return L.accLines == 0;
     return L.numSends <= 6 && L.mixLines >= 1 && L.mixLines <= 32 && L.wetChannels <= 32u;
 }

@@ -2,7 +2,7 @@
 and past the loop end, one-shot voices at and past the buffer end, tiny buffers -- LoadBufferStatic's branches
 (core/voice.cpp:500-544), the past-the-loop-end rule (:1015-1019) and the position wrap after the update (:1139-1146),
 which every voice kernel restates (csrc/wave_common.hpp GatherCovers / GatherStaticT / GatherIsLinear, dev_voice.hpp
-FillFromStatic, voice_slice.hip GatherSlice, and the position update of each kernel).
+FillFromStatic, and the position update of each kernel).
 
 Driven through any object with the oracle_lib.Scene interface.  `scene(step)` builds the case list of one pitch;
 `classify` names the branch the kernels' register gather takes for a voice's first chunk, and every case asserts that

@@ -16,8 +16,8 @@ DELAYS = {1: 1, 2: 37, 3: 700, 5: 1023, 6: 1024, 7: 1500, 9: 2500, 10: 64, 12: 5
 TODO = (1024, 700, 1024, 1024, 300)
 
 
-def run(lib, mhr, hrtf, sends, nvoices=14, stop_unstarted=(7,), split=False, on_scene=None):
-    """buses and integer voice state after every update of TODO.  split: every update's buses as a dict of float64 arrays
+def run(lib, mhr, hrtf, sends, nvoices=14, stop_unstarted=(7,), split=False, on_scene=None, todo=TODO):
+    """buses and integer voice state after every update of `todo`.  split: every update's buses as a dict of float64 arrays
     ("dry" -- dry and real lines --, "accum", "wet0", "wet1") instead of one vector; on_scene: called with the scene before
     the first update"""
     if hrtf:
@@ -48,7 +48,7 @@ def run(lib, mhr, hrtf, sends, nvoices=14, stop_unstarted=(7,), split=False, on_
         if v in DELAYS:
             sc.set_start_delay(v, DELAYS[v])
     out, ints = [], []
-    for k, n in enumerate(TODO):
+    for k, n in enumerate(todo):
         if k == 1:
             for v in stop_unstarted:                        # still waiting for its start: becomes Stopped without a sound
                 sc.set_state(v, ol.VOICE_STOPPING)
@@ -76,7 +76,6 @@ CASES = {
     "dry lines fast (stream rows)": dict(hrtf=False, sends=0, exact=False, flags=0),
     "dry lines + sends exact": dict(hrtf=False, sends=2, exact=True, flags=0),
     "dry lines + sends fast (rows in LDS)": dict(hrtf=False, sends=2, exact=False, flags=0),
-    "dry lines + sends fast (a wavefront per slice)": dict(hrtf=False, sends=2, exact=False, flags=128),      # OALGPU_CTX_SLICE_LINES
     "dry lines + sends fast (stream rows)": dict(hrtf=False, sends=2, exact=False, flags=8),                  # OALGPU_CTX_STREAM_ROWS
 }
 

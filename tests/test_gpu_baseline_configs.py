@@ -96,7 +96,7 @@ def close_to(got, want, what, terms=(1, 1)):
 
 
 def run_config(config, nvoices, mhr_path, todo=(1024, 1024, 1024, 1024), check_at=None, sample_fmt="f32", ctx_flags=0, via_blocks=False,
-               expect_kernel=None, resident_fits=True, vpg=0):
+               expect_kernel=None, resident_fits=True, vpg=0, capture=None):
     """check_at: the updates (0-based) after which buses and voice states are compared (None: every one).  Between
     checkpoints nothing of the product is read: its two-stream pipeline runs on unsynchronised, as in the bench.
     via_blocks: the product takes every update's parameters as a parameter block resident in HBM and runs the updates up to
@@ -104,7 +104,9 @@ def run_config(config, nvoices, mhr_path, todo=(1024, 1024, 1024, 1024), check_a
     OALGPU_CTX_APPLY_IN_VOICE_KERNEL / _FUSED_REDUCE / _RESIDENT contexts differ from the plain one.
     resident_fits: an OALGPU_CTX_RESIDENT context's grid fits the device at once -- the resident launch runs every update; False:
     the context gives the resident launch up and launches per update (the results are held to the reference all the same).
-    vpg: bench.build_scene's voices_per_group."""
+    vpg: bench.build_scene's voices_per_group.
+    capture: a list that receives the product's own buses and voice states (as bytes) at every checkpoint, for a caller that
+    compares two runs of the product with each other."""
     import oalgpu
     from oalgpu import synth
     import bench
@@ -178,6 +180,9 @@ def run_config(config, nvoices, mhr_path, todo=(1024, 1024, 1024, 1024), check_a
             g, o = gsc.voice_state(v), osc.voice_state(v)
             assert (g.play_state, g.position, g.position_frac, g.has_buffer, g.fading) == \
                 (o.play_state, o.position, o.position_frac, o.has_buffer, o.fading), (config, k, v)
+        if capture is not None:
+            capture.append((got_dry[:, :n].tobytes(), [gsc.wet(s)[:, :n].tobytes() for s in range(nslots)],
+                            [bytes(gsc.voice_state(v)) for v in range(nvoices)]))
     assert sounded, "the scene must actually sound"
     # float state of a sample of voices after the last update
     for v in range(0, nvoices, 97):
@@ -227,20 +232,13 @@ def test_config4_stream_rows(synth_mhr):
     run_config(4, 8192, synth_mhr, ctx_flags=oalgpu.CTX_STREAM_ROWS, expect_kernel="VoiceWaveKernel")
 
 
-def test_config4_a_wavefront_per_slice(synth_mhr):
-    """OALGPU_CTX_SLICE_LINES: the 21 mix lines in the registers of four wavefronts that own a 256-frame slice each
-    (csrc/voice_slice.hip) -- nothing of a voice's rows leaves the CU -- against the reference at full size."""
-    import oalgpu
-    run_config(4, 8192, synth_mhr, ctx_flags=oalgpu.CTX_SLICE_LINES, expect_kernel="VoiceSliceKernel")
-
-
 def test_config4_rows_in_lds_by_name(synth_mhr):
     """OALGPU_CTX_ROW_SLICES names the default form (include/oalgpu.h): the same kernel, the same results."""
     import oalgpu
     run_config(4, 8192, synth_mhr, ctx_flags=oalgpu.CTX_ROW_SLICES, expect_kernel="VoiceRowsKernel")
 
 
-PATHS = {"stream rows": (8, "VoiceWaveKernel"), "a wavefront per slice": (128, "VoiceSliceKernel"), "rows in LDS": (0, "VoiceRowsKernel")}
+PATHS = {"stream rows": (8, "VoiceWaveKernel"), "rows in LDS": (0, "VoiceRowsKernel")}
 
 
 @pytest.mark.parametrize("path", list(PATHS))
@@ -289,12 +287,6 @@ def test_config4_stream_rows_after_updates_1_2_8_50(synth_mhr):
     import oalgpu
     run_config(4, 8192, synth_mhr, todo=(1024,) * 50, check_at=SCHEDULE, sample_fmt="i16", ctx_flags=oalgpu.CTX_STREAM_ROWS,
                expect_kernel="VoiceWaveKernel")
-
-
-def test_config4_a_wavefront_per_slice_after_updates_1_2_8_50(synth_mhr):
-    import oalgpu
-    run_config(4, 8192, synth_mhr, todo=(1024,) * 50, check_at=SCHEDULE, sample_fmt="i16", ctx_flags=oalgpu.CTX_SLICE_LINES,
-               expect_kernel="VoiceSliceKernel")
 
 
 @pytest.mark.parametrize("sample_fmt", ["f32", "i16"])

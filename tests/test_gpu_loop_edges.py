@@ -24,7 +24,6 @@ FORMS = {   # name: (math mode, context flags, scene form, the kernel that must 
     "register_lines": ("fast", 0, "dry", "VoiceWaveKernel<17, 64, 1, false, false, false, DeviceLayout, 6>"),
     "rows": ("fast", 0, "dry_sends", "VoiceRowsKernel"),
     "stream_rows": ("fast", "CTX_STREAM_ROWS", "dry_sends", "VoiceWaveKernel<17, 64, 1, true>"),
-    "slice_lines": ("fast", "CTX_SLICE_LINES", "dry_sends", "VoiceSliceKernel<24>"),
     "exact_hrtf": ("exact", 0, "hrtf", "VoiceMixKernel<true, LINES>"),
     "exact_dry_sends": ("exact", 0, "dry_sends", "VoiceMixKernel<true, LINES>"),
 }
