@@ -695,6 +695,51 @@ int oalgpu_comm_init_host(oalgpu_context *ctx, const char *name, int rank, int w
 int oalgpu_comm_info(oalgpu_context *ctx, int *rank, int *world, int *transport_ranks, char *kind, size_t kind_size);
 int oalgpu_comm_destroy(oalgpu_context *ctx);
 
+/* ---- several contexts on one device: ProcessContexts (alc/alu.cpp:2177-2273) --------------------------------
+ * A context is the reference's DeviceBase and its first ContextBase.  Further ContextBases of the same device are
+ * contexts of their own that are ATTACHED to it: the device context's update then is one renderSamples.
+ *
+ * line_map has num_dry + num_real entries of `ctx`: entry i is the line of device_ctx's dry + real block
+ * (0 .. num_dry + num_real - 1, dry lines first, then real lines) that ctx's line i adds into; -1: the line goes nowhere.
+ *
+ * From the attach on, every update of device_ctx (oalgpu_mix_update, oalgpu_mix_update_run, oalgpu_mix_voices +
+ * oalgpu_post_process and their _overlapped forms) does, for every attached context in attach order and with the same
+ * samples_to_do:
+ *   - its voice mix and bus reduction (what oalgpu_mix_voices does for it: callbacks serviced, inits flushed), submitted
+ *     in front of device_ctx's own voice kernel, so that the kernels run side by side;
+ *   - where the update post-processes, its own effect slots (RunEffects);
+ * and then, behind device_ctx's own reduction and in front of device_ctx's effect slots, post-process, limiter, distance
+ * compensation and output, ONE launch (BusMergeKernel) adds the attached contexts' dry + real lines into device_ctx's
+ * through their maps: a destination line's frames [0, samples_to_do) become
+ *   (device_ctx's own value) + attached 0 + attached 1 + ...        in attach order (within a context: in line order),
+ * one fp32 add per contributor and sample: the same inputs always give the same bits.  An update that does not
+ * post-process merges nothing: the attached contexts have mixed their voices, and their buses are readable on their own
+ * (oalgpu_read_dry(ctx) always is).  Nothing on this path waits on the host: the merge waits by event for each attached
+ * context's last launch of the update, and an attached context's next reduction waits by event for the merge.
+ *
+ * An attached context keeps every setter of voices, buffers, parameters, pan, slots and effects.  It has no post stage:
+ * what the attach refuses to find installed (below) the setters refuse to install while it is attached (removals stay
+ * open).  oalgpu_mix_update*, oalgpu_mix_voices*, oalgpu_post_process* on it return
+ * OALGPU_ERR_INVALID (its device context updates it).  oalgpu_sync(device_ctx) and device_ctx's read-backs also wait
+ * for the attached contexts' work of that update.
+ *
+ * oalgpu_context_attach refuses with OALGPU_ERR_INVALID, changing nothing: a null argument or device_ctx == ctx; ctx
+ * already attached; device_ctx itself attached, or ctx with attached contexts (no nesting); different device ordinals or
+ * sample rates; ctx an HRTF context (HRTF voices belong to the device context); ctx with a B-Format decoder or any other
+ * post-process kind, a limiter, distance compensation or an output conversion installed; either context with a
+ * collective (oalgpu_comm_init*, which in turn refuses a context that has, or is, an attachment: sharded devices with
+ * attached contexts are not supported); ctx on a caller-owned stream (and oalgpu_set_stream with a stream refuses an
+ * attached context); a map entry out of range.
+ *
+ * Both calls wait for the work in flight of both contexts.  oalgpu_context_destroy(ctx) detaches ctx first; destroying
+ * a device context detaches all its contexts, which live on as independent contexts.  After the detach both contexts
+ * behave as if they had never been attached.  While at least one context is attached, the device context does not use
+ * the resident launch (OALGPU_CTX_RESIDENT) and does not fuse reduction and post-process (OALGPU_CTX_FUSED_REDUCE);
+ * a deferred update (OALGPU_CTX_APPLY_IN_VOICE_KERNEL) submits the attached contexts with its own submission, and a
+ * setter of an attached context submits it first.  A context without attachments runs exactly what it ran before. */
+int oalgpu_context_attach(oalgpu_context *device_ctx, oalgpu_context *ctx, const int32_t *line_map);
+int oalgpu_context_detach(oalgpu_context *ctx);
+
 /* Mixing state of one voice after the last update (the fields Voice::mix mutates). */
 typedef struct oalgpu_voice_state {
     int32_t  play_state;

@@ -300,10 +300,13 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     return OALGPU_OK;
 }
 
+static void DetachForDestroy(oalgpu_context *ctx);
+
 void oalgpu_context_destroy(oalgpu_context *ctx)
 {
     if(!ctx) return;
     (void)UseDevice(ctx->desc.device);          // (a resident voice kernel is told to leave)
+    if(ctx->attachedTo || !ctx->attached.empty()) DetachForDestroy(ctx);
     if(ctx->res.pendingBlock) { ctx->res.pendingBlock->heldBy = nullptr; ctx->res.pendingBlock = nullptr; }
     (void)FlushPendingMix(ctx);
     (void)hipStreamSynchronize(ctx->stream);
@@ -477,7 +480,7 @@ bool ResidentWanted(const oalgpu_context *c, int post_process)
     const auto &R = c->res;
     return R.enabled && !R.failed && WaveKernelHasResident(c->L) && post_process && c->hrtfLoaded && c->directSet && !c->timing && c->cbVoices.empty()
         && c->initPending.empty() && c->carryAccum && !c->comm && !c->pendingMix.active && c->useWave && c->ownStream && !c->serialOnly
-        && c->L.numReal >= 2 && c->L.numSlots == 0;
+        && c->L.numReal >= 2 && c->L.numSlots == 0 && c->attached.empty();
 }
 
 // a parameter block that was waiting for a resident update is applied the launched way (the caller has parked the kernel)
@@ -717,14 +720,55 @@ static int ResidentSubmit(oalgpu_context *c, uint32_t samples_to_do)
     return OALGPU_OK;
 }
 
+static int RefuseAttached(const oalgpu_context *c, const char *who)
+{
+    if(!c->attachedTo) return OALGPU_OK;
+    return Fail(OALGPU_ERR_INVALID, std::string(who) + ": the context is attached (oalgpu_context_attach): its device context updates it");
+}
+
+static int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do);
+
+// (device context) the attached contexts' voices and reductions of this update, each on its own main stream, in front of the
+// device context's own voice kernel: the kernels run side by side
+static int MixAttached(oalgpu_context *c, uint32_t samples_to_do)
+{
+    for(oalgpu_context *a : c->attached) { if(int rc = MixVoicesSerial(a, samples_to_do)) return rc; }
+    return OALGPU_OK;
+}
+
+// (device context) behind its own reduction on stream `s`, in front of its effect slots and post stage: the attached contexts'
+// effect slots, then their lines into the device context's (BusMergeKernel) once their last launches are through
+static int MergeAttached(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
+{
+    for(oalgpu_context *a : c->attached)
+    {
+        if(int rc = RunEffects(a, a->stream, samples_to_do)) return rc;
+        HIP_TRY(hipEventRecord(a->evBusFinal, a->stream));
+        HIP_TRY(hipStreamWaitEvent(s, a->evBusFinal, 0));
+    }
+    LaunchBusMerge(s, c->mergeHeads.p, c->mergeRows.p, c->mergeLines, samples_to_do);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evMerged, s));
+    c->mergeInFlight = true;
+    return OALGPU_OK;
+}
+
 int oalgpu_mix_voices(oalgpu_context *c, uint32_t samples_to_do)
 {
     if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
+    if(int rc = RefuseAttached(c, "oalgpu_mix_voices")) return rc;
+    return MixVoicesSerial(c, samples_to_do);
+}
+
+// oalgpu_mix_voices; also what a device context does for each of its attached contexts
+static int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do)
+{
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
     if(int rc = UseCtx(c)) return rc;
     if(int rc = FlushInits(c)) return rc;
     if(int rc = JoinPost(c)) return rc;
     if(!c->cbVoices.empty()) { if(int rc = ServiceCallbacks(c, samples_to_do)) return rc; }
+    if(!c->attached.empty()) { if(int rc = MixAttached(c, samples_to_do)) return rc; }
     c->outRingWritten = false;
     if(c->useWave)    // (timing: the two events are bound to the dispatch itself -- the kernel's own start and end)
         HIP_TRY(LaunchVoiceWave(c->stream, c->L, samples_to_do, c->profArg(), c->timing ? c->evStart : nullptr, c->timing ? c->evVoice : nullptr));
@@ -734,6 +778,8 @@ int oalgpu_mix_voices(oalgpu_context *c, uint32_t samples_to_do)
         HIP_TRY(LaunchVoiceMix(c->stream, c->exact, c->L, samples_to_do, c->carryAccum));
         if(c->timing) HIP_TRY(hipEventRecord(c->evVoice, c->stream));
     }
+    // (an attached context's bus block is single-buffered: the device context's merge of the update before reads it)
+    if(c->attachedTo && c->attachedTo->mergeInFlight) HIP_TRY(hipStreamWaitEvent(c->stream, c->attachedTo->evMerged, 0));
     // the wavefront kernel leaves the carried HRTF accumulator tail to the reduction
     LaunchBusReduce(c->stream, c->L, samples_to_do, CarrySource(c, c->useWave && c->carryAccum));
     HIP_TRY(hipGetLastError());
@@ -745,8 +791,10 @@ int oalgpu_mix_voices(oalgpu_context *c, uint32_t samples_to_do)
 int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
 {
     if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
+    if(int rc = RefuseAttached(c, "oalgpu_post_process")) return rc;
     if(int rc = UseCtx(c)) return rc;
     if(int rc = JoinPost(c)) return rc;
+    if(!c->attached.empty()) { if(int rc = MergeAttached(c, c->stream, samples_to_do)) return rc; }
     if(int rc = RunEffects(c, c->stream, samples_to_do)) return rc;
     if(!c->L.hrtf)
     {
@@ -778,6 +826,7 @@ static int RunMixUpdate(oalgpu_context *c, uint32_t samples_to_do, int post_proc
 int oalgpu_mix_update(oalgpu_context *c, uint32_t samples_to_do, int post_process)
 {
     if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
+    if(int rc = RefuseAttached(c, "oalgpu_mix_update")) return rc;
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
     if(c->res.cooldown) --c->res.cooldown;
     else if(ResidentWanted(c, post_process))
@@ -804,6 +853,8 @@ int BeginSetter(oalgpu_context *c, const char *who)
 
 int FlushPendingMix(oalgpu_context *c, oalgpu_param_block *next)
 {
+    // (a setter of an attached context: the device context's deferred update mixes this context's voices as they were)
+    if(c->attachedTo) { if(int rc = FlushPendingMix(c->attachedTo)) return rc; }
     if(!c->pendingMix.active) return OALGPU_OK;
     c->pendingMix.active = false;
     return RunMixUpdate(c, c->pendingMix.samples, c->pendingMix.post, next);
@@ -824,7 +875,7 @@ static int RunMixUpdate(oalgpu_context *c, uint32_t samples_to_do, int post_proc
         return OALGPU_OK;
     }
     c->fuseReduce = post_process && !c->comm && c->L.hrtf && c->L.numSlots == 0 && c->L.numReal >= 2 && !c->timing
-        && (c->desc.flags & OALGPU_CTX_FUSED_REDUCE);
+        && (c->desc.flags & OALGPU_CTX_FUSED_REDUCE) && c->attached.empty();
     const int rcv = oalgpu_mix_voices_overlapped(c, samples_to_do);
     c->fuseReduce = false;
     if(rcv) { c->reduceHeld = false; return rcv; }
@@ -838,6 +889,7 @@ int oalgpu_mix_update_run(oalgpu_context *c, oalgpu_param_block *const *param_bl
     int post_process)
 {
     if(!c || count == 0) return Fail(OALGPU_ERR_INVALID, "oalgpu_mix_update_run: bad arguments");
+    if(int rc = RefuseAttached(c, "oalgpu_mix_update_run")) return rc;
     for(uint32_t i = 0; i < count; ++i)
     {
         if(param_blocks && param_blocks[i]) { if(int rc = oalgpu_param_block_apply(c, param_blocks[i])) return rc; }
@@ -851,10 +903,12 @@ int oalgpu_mix_voices_overlapped(oalgpu_context *c, uint32_t samples_to_do)
     if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
     if(!(c->useWave && c->ownStream))
         return Fail(OALGPU_ERR_INVALID, "oalgpu_mix_voices_overlapped: needs a FAST context (wavefront kernel) on its own streams");
+    if(int rc = RefuseAttached(c, "oalgpu_mix_voices_overlapped")) return rc;
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
     if(int rc = UseCtx(c)) return rc;
     if(int rc = FlushInits(c)) return rc;
     if(!c->cbVoices.empty()) { if(int rc = ServiceCallbacks(c, samples_to_do)) return rc; }
+    if(!c->attached.empty()) { if(int rc = MixAttached(c, samples_to_do)) return rc; }
     c->outRingWritten = false;
     const uint32_t p = c->parity;
     DeviceLayout L = c->L;
@@ -901,10 +955,12 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
     if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
     if(!(c->useWave && c->ownStream))
         return Fail(OALGPU_ERR_INVALID, "oalgpu_post_process_overlapped: needs a FAST context (wavefront kernel) on its own streams");
+    if(int rc = RefuseAttached(c, "oalgpu_post_process_overlapped")) return rc;
     if(post_process && c->L.hrtf && c->L.numReal < 2) return Fail(OALGPU_ERR_INVALID, "HRTF post-process needs two real output lines");
     if(int rc = UseCtx(c)) return rc;
     const DeviceLayout &L = c->L;
     bool postDoneBound = false;
+    if(post_process && !c->attached.empty()) { if(int rc = MergeAttached(c, c->postStream, samples_to_do)) return rc; }
     if(post_process) { if(int rc = RunEffects(c, c->postStream, samples_to_do)) return rc; }
     if(post_process && L.hrtf)
     {
@@ -937,8 +993,126 @@ int oalgpu_sync(oalgpu_context *c)
     if(c->postStream) HIP_TRY(hipStreamSynchronize(c->postStream));
     c->postPending = false;
     c->updatesKnownDone = c->updatesSubmitted;
+    for(oalgpu_context *a : c->attached)
+    {   // (their work of the update: the voices and reductions of an update that merged nothing are waited for too)
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        if(a->postStream) HIP_TRY(hipStreamSynchronize(a->postStream));
+        a->postPending = false;
+        a->updatesKnownDone = a->updatesSubmitted;
+    }
+    c->mergeInFlight = false;
     if(c->res.ready) { ResidentCollectTimes(c, true); if(int rc = ResidentCheckError(c)) return rc; }
     return OALGPU_OK;
+}
+
+// ---- several contexts on one device (ProcessContexts, alc/alu.cpp:2177-2273; include/oalgpu.h) ----
+// The merge's table of a device context, from its attached contexts' maps: per destination line the contributing lines in
+// attach order (within a context: in line order).  The caller has waited for everything that may still read the old table.
+static int RebuildMergeTable(oalgpu_context *d)
+{
+    const uint32_t lines = d->L.numDry + d->L.numReal;
+    std::vector<BusMergeHead> heads;
+    std::vector<BusMergeRow> rows;
+    std::vector<int32_t> last(lines, -1);
+    for(uint32_t line = 0; line < lines; ++line)
+        for(const oalgpu_context *a : d->attached)
+            for(size_t i = 0; i < a->attachMap.size(); ++i)
+            {
+                if(a->attachMap[i] != int32_t(line)) continue;
+                const int32_t r = int32_t(rows.size());
+                rows.push_back(BusMergeRow{a->L.bus + i * kLine, -1, 0u});
+                if(last[line] < 0) heads.push_back(BusMergeHead{d->L.bus + size_t{line} * kLine, r, 0u});
+                else rows[size_t(last[line])].next = r;
+                last[line] = r;
+            }
+    // (built beside the old table and swapped in whole: a failed allocation leaves the old one, and its contexts merged)
+    DevBuf<BusMergeHead> newHeads;
+    DevBuf<BusMergeRow> newRows;
+    if(!heads.empty())
+    {
+        HIP_TRY(newHeads.alloc(heads.size())); HIP_TRY(newHeads.upload(heads.data(), heads.size()));
+        HIP_TRY(newRows.alloc(rows.size())); HIP_TRY(newRows.upload(rows.data(), rows.size()));
+    }
+    std::swap(d->mergeHeads.p, newHeads.p); std::swap(d->mergeHeads.n, newHeads.n);
+    std::swap(d->mergeRows.p, newRows.p); std::swap(d->mergeRows.n, newRows.n);
+    d->mergeLines = uint32_t(heads.size());
+    return OALGPU_OK;
+}
+
+static void Unlink(oalgpu_context *a)
+{
+    oalgpu_context *d = a->attachedTo;
+    d->attached.erase(std::remove(d->attached.begin(), d->attached.end(), a), d->attached.end());
+    a->attachedTo = nullptr;
+    a->attachMap.clear();
+    d->mergeInFlight = false;
+}
+
+int oalgpu_context_attach(oalgpu_context *d, oalgpu_context *a, const int32_t *line_map)
+{
+    const std::string w = "oalgpu_context_attach: ";
+    if(!d || !a || !line_map) return Fail(OALGPU_ERR_INVALID, w + "null argument");
+    if(d == a) return Fail(OALGPU_ERR_INVALID, w + "a context cannot be attached to itself");
+    if(a->attachedTo) return Fail(OALGPU_ERR_INVALID, w + "the context is already attached");
+    if(d->attachedTo) return Fail(OALGPU_ERR_INVALID, w + "the device context is itself attached (no nesting)");
+    if(!a->attached.empty()) return Fail(OALGPU_ERR_INVALID, w + "the context has attached contexts of its own (no nesting)");
+    if(d->desc.device != a->desc.device) return Fail(OALGPU_ERR_INVALID, w + "the contexts are on different devices");
+    if(d->desc.sample_rate != a->desc.sample_rate) return Fail(OALGPU_ERR_INVALID, w + "the contexts have different sample rates");
+    if(a->L.hrtf) return Fail(OALGPU_ERR_INVALID, w + "an HRTF context cannot be attached (HRTF voices belong to the device context)");
+    if(a->post != PostKind::None) return Fail(OALGPU_ERR_INVALID, w + "the context has a post-process installed (the device context post-processes)");
+    if(a->limOn) return Fail(OALGPU_ERR_INVALID, w + "the context has an output limiter (the device context limits)");
+    if(a->distLines) return Fail(OALGPU_ERR_INVALID, w + "the context has distance compensation (the device context compensates)");
+    if(a->outType != OALGPU_OUT_F32 || a->ditherDepth > 0.0f)
+        return Fail(OALGPU_ERR_INVALID, w + "the context has an output conversion (oalgpu_set_output: the device context converts)");
+    if(d->comm || a->comm) return Fail(OALGPU_ERR_INVALID, w + "a context with a collective (oalgpu_comm_init) takes and is no attachment");
+    if(!a->ownStream) return Fail(OALGPU_ERR_INVALID, w + "the context is on a caller-owned stream (oalgpu_set_stream)");
+    const uint32_t srcLines = a->L.numDry + a->L.numReal, dstLines = d->L.numDry + d->L.numReal;
+    for(uint32_t i = 0; i < srcLines; ++i)
+        if(line_map[i] < -1 || line_map[i] >= int32_t(dstLines))
+            return Fail(OALGPU_ERR_INVALID, w + "map entry " + std::to_string(i) + " is out of range (-1 .. " + std::to_string(dstLines - 1u) + ")");
+    // the work in flight of both (a resident voice kernel leaves, a deferred update is submitted)
+    if(int rc = oalgpu_sync(d)) return rc;
+    if(int rc = oalgpu_sync(a)) return rc;
+    // ordering between streams of one device only: no system-scope fence (see oalgpu_context_create)
+    if(!a->evBusFinal) HIP_TRY(hipEventCreateWithFlags(&a->evBusFinal, hipEventDisableTiming | hipEventDisableSystemFence));
+    if(!d->evMerged) HIP_TRY(hipEventCreateWithFlags(&d->evMerged, hipEventDisableTiming | hipEventDisableSystemFence));
+    a->attachMap.assign(line_map, line_map + srcLines);
+    a->attachedTo = d;
+    d->attached.push_back(a);
+    if(int rc = RebuildMergeTable(d))
+    {
+        Unlink(a);
+        (void)RebuildMergeTable(d);
+        return rc;
+    }
+    return OALGPU_OK;
+}
+
+int oalgpu_context_detach(oalgpu_context *a)
+{
+    if(!a) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_detach: null argument");
+    oalgpu_context *d = a->attachedTo;
+    if(!d) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_detach: the context is not attached");
+    if(int rc = oalgpu_sync(d)) return rc;          // (waits for the attached contexts' streams as well)
+    Unlink(a);
+    return RebuildMergeTable(d);
+}
+
+// oalgpu_context_destroy of a context that has, or is, an attachment: the links go whatever the device says
+static void DetachForDestroy(oalgpu_context *ctx)
+{
+    if(oalgpu_context *d = ctx->attachedTo)
+    {
+        (void)oalgpu_sync(d);
+        Unlink(ctx);
+        (void)RebuildMergeTable(d);
+    }
+    if(!ctx->attached.empty())
+    {
+        (void)oalgpu_sync(ctx);
+        while(!ctx->attached.empty()) Unlink(ctx->attached.back());
+        ctx->mergeLines = 0;
+    }
 }
 
 int oalgpu_set_timing(oalgpu_context *c, int enable)

@@ -207,6 +207,8 @@ int oalgpu_comm_init(oalgpu_context *c, const void *unique_id, size_t size, int 
     if(!c || !unique_id || size < sizeof(ncclUniqueId) || world < 1 || rank < 0 || rank >= world)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init: bad arguments");
     if(c->comm) return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init: the context already has a communicator");
+    if(c->attachedTo || !c->attached.empty())
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init: not on a context that has, or is, an attachment (oalgpu_context_attach)");
     if(!c->cbVoices.empty()) return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init: not on a context with callback sources");
     RcclApi &a = Rccl();
     if(!a.ok) return Fail(OALGPU_ERR_NO_DEVICE, a.why);
@@ -230,6 +232,8 @@ int oalgpu_comm_init_host(oalgpu_context *c, const char *name, int rank, int wor
     if(!c || !name || name[0] != '/' || world < 1 || world > int(HostTransport::kMaxWorld) || rank < 0 || rank >= world)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init_host: bad arguments");
     if(c->comm) return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init_host: the context already has a communicator");
+    if(c->attachedTo || !c->attached.empty())
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init_host: not on a context that has, or is, an attachment (oalgpu_context_attach)");
     if(!c->cbVoices.empty()) return Fail(OALGPU_ERR_INVALID, "oalgpu_comm_init_host: not on a context with callback sources");
     if(int rc = UseCtx(c)) return rc;
     if(int rc = oalgpu_sync(c)) return rc;

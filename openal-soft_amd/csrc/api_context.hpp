@@ -36,6 +36,7 @@
 #include "../host/tables.hpp"
 #include "api_util.hpp"
 #include "kernels.hpp"
+#include "bus_merge.hpp"
 #include "reverb_dev.hpp"
 
 using namespace oalgpu;
@@ -195,6 +196,18 @@ struct oalgpu_context {
     // right behind the partial-bus reduction, on the stream that runs it
     struct BusTransport *comm{nullptr};
     int commRank{0}, commWorld{1};
+    // several contexts on one device (oalgpu_context_attach: ProcessContexts, alc/alu.cpp:2177-2273).  The device context
+    // updates its attached contexts -- their voices before its own voice kernel, their effect slots before the merge -- and ONE
+    // launch (BusMergeKernel) adds their dry + real lines into its own behind its reduction.
+    oalgpu_context *attachedTo{nullptr};   // (attached context) the device context that updates it
+    std::vector<int32_t> attachMap;        // (attached context) its line i -> line of the device context's dry + real block, or -1
+    hipEvent_t evBusFinal{nullptr};        // (attached context) behind its last launch of an update: its reduction or its last effect kernel
+    std::vector<oalgpu_context*> attached; // (device context) in attach order
+    DevBuf<BusMergeHead> mergeHeads;       // (device context) the merge's table, rebuilt by attach / detach: a head per
+    DevBuf<BusMergeRow> mergeRows;         // destination line that has contributors, a row per contributing line
+    uint32_t mergeLines{0};
+    hipEvent_t evMerged{nullptr};          // (device context) behind the merge: the attached contexts' next reductions wait for it
+    bool mergeInFlight{false};             // a merge was launched since the host last waited for the device context
     // the stage behind the buses (api_poststage.hip): the one post-process of a non-HRTF context and what each kind keeps
     PostKind post{PostKind::None};
     // the B-Format decoder (oalgpu_set_bformat_decoder: AmbiDec, and under Stabilizer and Bs2b)
@@ -333,6 +346,7 @@ struct oalgpu_context {
         for(uint32_t k = 0; k < ResidentState::kEv; ++k)
             for(hipEvent_t e : {res.evStart[k], res.evStop[k]}) if(e) (void)hipEventDestroy(e);
         if(res.reduceStream) (void)hipStreamDestroy(res.reduceStream);
+        for(hipEvent_t e : {evBusFinal, evMerged}) if(e) (void)hipEventDestroy(e);
         if(evStart) (void)hipEventDestroy(evStart);
         if(evVoice) (void)hipEventDestroy(evVoice);
         if(evEnd) (void)hipEventDestroy(evEnd);

@@ -148,6 +148,8 @@ int oalgpu_voice_events_wait(oalgpu_context *c, uint32_t ticket, oalgpu_voice_ev
 int oalgpu_set_stream(oalgpu_context *c, void *hip_stream)
 {
     if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
+    if(hip_stream && c->attachedTo)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_stream: an attached context (oalgpu_context_attach) stays on its own streams");
     if(int rc = UseCtx(c)) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if(c->postStream) HIP_TRY(hipStreamSynchronize(c->postStream));
@@ -180,6 +182,8 @@ int oalgpu_set_output(oalgpu_context *c, int sample_type, float dither_depth, ui
     if(int rc = BeginSetter(c, "oalgpu_set_output")) return rc;
     if(sample_type < OALGPU_OUT_I8 || sample_type > OALGPU_OUT_F32 || dither_depth < 0.0f)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output: bad arguments");
+    if(c->attachedTo && (sample_type != OALGPU_OUT_F32 || dither_depth > 0.0f))
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_set_output: the context is attached (oalgpu_context_attach): its device context has the post stage");
     c->outType = sample_type; c->ditherDepth = dither_depth; c->ditherSeed = dither_seed;
     return OALGPU_OK;
 }

@@ -19,10 +19,15 @@ static const uint32_t kAcceptedOver[6] = {
     /* Tsme       */ Bit(PostKind::None) | Bit(PostKind::Tsme),
 };
 
+// An attached context (oalgpu_context_attach) has no post stage: what the attach refuses to find installed cannot be installed
+// afterwards either.  Removals stay open.
+static const char kAttachedHasNoPostStage[] = "the context is attached (oalgpu_context_attach): its device context has the post stage";
+
 static int CheckPost(const oalgpu_context *c, const char *who, PostKind want)
 {
     const std::string w = std::string(who) + ": ";
     if(c->L.hrtf) return Fail(OALGPU_ERR_INVALID, w + "an HRTF context post-processes with MixDirectHrtf");
+    if(c->attachedTo && want != PostKind::None) return Fail(OALGPU_ERR_INVALID, w + kAttachedHasNoPostStage);
     if(kAcceptedOver[uint32_t(want)] & Bit(c->post)) return OALGPU_OK;
     const char *have = kPostNames[uint32_t(c->post)];
     if(want == PostKind::None) return Fail(OALGPU_ERR_INVALID, w + "the context's " + have + " decodes with it (remove that first)");
@@ -92,6 +97,7 @@ uint32_t oalgpu_limiter_look_ahead(const oalgpu_limiter_params *params)
 int oalgpu_set_output_limiter(oalgpu_context *c, const oalgpu_limiter_params *params)
 {
     if(int rc = BeginSetter(c, "oalgpu_set_output_limiter")) return rc;
+    if(params && c->attachedTo) return Fail(OALGPU_ERR_INVALID, std::string("oalgpu_set_output_limiter: ") + kAttachedHasNoPostStage);
     const uint32_t nlines = RealOutLines(c);
     LimiterConsts k{};
     if(params)
@@ -260,6 +266,7 @@ int oalgpu_set_distance_comp(oalgpu_context *c, uint32_t n, const uint32_t *dela
     const bool set = n != 0 && delays && gains;
     if(set)
     {
+        if(c->attachedTo) return Fail(OALGPU_ERR_INVALID, std::string("oalgpu_set_distance_comp: ") + kAttachedHasNoPostStage);
         if(c->L.hrtf)
             return Fail(OALGPU_ERR_INVALID, "oalgpu_set_distance_comp: an HRTF context has no speaker distances to compensate");
         if(n > RealOutLines(c))

@@ -378,6 +378,7 @@ class Scene:
     def __init__(self, api, sample_rate=48000, num_dry=3, num_real=0, num_sends=0, num_slots=0,
                  wet_channels=4, hrtf=False, max_voices=64, max_buffers=64, voices_per_group=0, flags=None):
         self.h = None
+        self._device_scene = None       # (attached scenes) the scene of the device context: kept alive for as long as this one is
         self.api = api
         self.desc = ContextDesc(api.device, api.mode, sample_rate, num_dry, num_real, num_sends,
                                 num_slots, wet_channels, 1 if hrtf else 0, max_voices, max_buffers,
@@ -393,12 +394,30 @@ class Scene:
 
     def close(self):
         if getattr(self, "h", None):
-            lib.oalgpu_context_destroy(self.h)
+            lib.oalgpu_context_destroy(self.h)      # (detaches the context, and every context attached to it, first)
             self.h = None
+        self._device_scene = None
 
     def __del__(self):
         if lib is not None:             # module globals are gone when the interpreter shuts down
             self.close()
+
+    # several contexts on one device (oalgpu_context_attach): this scene is the device context
+    def attach(self, child, line_map):
+        """child's line i (dry lines, then real lines) adds into this scene's line line_map[i] (-1: nowhere) from the next
+        update on; this scene's updates then mix the child's voices too.  The child keeps this scene alive."""
+        lib.oalgpu_context_attach.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        m = np.ascontiguousarray(line_map, np.int32)
+        if m.size != child.desc.num_dry_channels + child.desc.num_real_channels:
+            raise OalgpuError("attach: line_map needs one entry per dry and real line of the attached scene")
+        check(lib.oalgpu_context_attach(self.h, child.h, m.ctypes.data_as(C.POINTER(C.c_int32))), "oalgpu_context_attach")
+        child._device_scene = self
+
+    def detach(self):
+        """this (attached) scene becomes an independent context again"""
+        lib.oalgpu_context_detach.argtypes = [C.c_void_p]
+        check(lib.oalgpu_context_detach(self.h), "oalgpu_context_detach")
+        self._device_scene = None
 
     def hrtf_info(self):
         info = HrtfInfo()
