@@ -834,7 +834,9 @@ int oalgpu_set_timing(oalgpu_context *ctx, int enable);
  *                         (alc/effects/compressor.cpp: envelope follower on wet channel 0, no gain ramp)
  * process: wet_in = the slot's wet bus (num_in x 1024; echo and dedicated use channel 0), out_lines = num_out_lines
  * x 1024, added to.  Like the reverb these keep the reference's operation order in both math modes: the output
- * is bit-identical to the reference's, except the modulator's sinusoid carrier (the GPU's sinf against libm). */
+ * is bit-identical to the reference's, except the modulator's sinusoid carrier (the GPU's sinf against libm).
+ * On a slot that has a target (oalgpu_slot_set_target below) out_lines is the target slot's wet bus: the caller resolves
+ * target_channels / gains against that slot's Wet mix parameters and creates the effect with num_out_lines = wet_channels. */
 enum oalgpu_effect_kind {
     OALGPU_EFFECT_EQUALIZER = 0, OALGPU_EFFECT_MODULATOR, OALGPU_EFFECT_ECHO, OALGPU_EFFECT_DEDICATED, OALGPU_EFFECT_COMPRESSOR,
     OALGPU_EFFECT_CHORUS, OALGPU_EFFECT_DISTORTION, OALGPU_EFFECT_AUTOWAH, OALGPU_EFFECT_VMORPHER, OALGPU_EFFECT_FSHIFTER,
@@ -1052,6 +1054,49 @@ int  oalgpu_reverb_skip(oalgpu_reverb *rev, uint32_t n);
 /* Attach to effect slot `slot` of a context (like oalgpu_slot_set_convolution): wet bus lines
  * 0..3 in, dry lines out.  NULL detaches. */
 int  oalgpu_slot_set_reverb(oalgpu_context *ctx, uint32_t slot, oalgpu_reverb *rev);
+
+/* ---- effect slot targets: a slot's effect feeds another slot's wet bus ------------------------------------------------
+ * AL_EFFECTSLOT_TARGET_SOFT (AL_SOFT_effect_target, al/auxeffectslot.cpp:504-520): a reverb into an equalizer, an echo
+ * into a reverb.  The effect leg of ProcessContexts (alc/alu.cpp:2209-2257) first sorts a context's slots so that a slot
+ * comes in front of the slot it targets (:2220-2249), and every effect then writes where GetEffectTarget points
+ * (alc/alu.cpp:627-632):
+ *     if(auto *const target = slot->Target) return EffectTarget{&target->Wet, nullptr};
+ *     return EffectTarget{&device->Dry, &device->RealOut};
+ *
+ * oalgpu_slot_set_target(ctx, slot, target_slot): target_slot -1 (the default) is the device's lines -- dry, then real.
+ * Otherwise everything attached to `slot` (its oalgpu_effect, oalgpu_convolution and oalgpu_reverb, in any combination)
+ * adds into the wet bus of `target_slot` of the same context: wet_channels lines of 1024 samples, the block
+ * oalgpu_read_wet(ctx, target_slot, ..) reads, in place of the dry + real block.  The caller resolves gains and target
+ * channels against the target slot's Wet mix parameters, as it does against the device's lines (oalgpu_effect_update
+ * above, oalgpu_convolution_set_*_gains, the reverb's pan gains), and creates the feeding effect with
+ * num_out_lines = wet_channels.  The call waits for the work in flight like the other slot setters; attached contexts
+ * (oalgpu_context_attach) keep it, and their slots chain among themselves before the merge.  A slot index cannot name
+ * another context's slot: targets stay within one context.
+ *
+ * Order: a slot's depth is 0 without a target, otherwise its target's depth + 1.  Every update path that runs the effect
+ * slots processes them by descending depth -- every slot of depth d before any slot of depth d - 1, the groups of the
+ * reference's partition loop -- and within one depth as without targets: convolutions and effects by ascending slot
+ * index, then that depth's EAX reverbs as one launch with their mix-out in slot order.  Two feeders of one target so add
+ * in ascending slot order.  The order changes only when a target is set.  A context in which no slot has a target runs
+ * exactly what it ran before.  After an update that post-processes, oalgpu_read_wet(target) returns the voices' sends
+ * plus what the feeders added (the reference modifies Wet.Buffer in place as well); the next update's reduction
+ * overwrites it.  An update with post_process == 0 leaves the wet buses as the voices wrote them.  A feeder whose
+ * target has nothing attached still adds into that wet bus, and nothing of it reaches the device's lines.
+ *
+ * oalgpu_slot_set_target refuses with OALGPU_ERR_INVALID, changing nothing: a null context; a slot or target out of
+ * range; target_slot == slot; a target that would close a cycle (al/auxeffectslot.cpp:511-516); an attached effect,
+ * reverb or convolution whose output lines exceed wet_channels.  The three oalgpu_slot_set_* calls apply the same rule
+ * from their side: on a slot that has a target they measure the object's output lines against wet_channels, on a slot
+ * without one against the device's lines as before.
+ *
+ * oalgpu_slot_target reads the target back.
+ *
+ * oalgpu_slot_order is the order rule itself, on the host, without a device: targets[num_slots] in, order[num_slots]
+ * (the processing order) and depth[num_slots] (may be NULL) out.  OALGPU_ERR_INVALID, with nothing written: a target
+ * below -1 or >= num_slots, a slot that targets itself, a cycle. */
+int  oalgpu_slot_set_target(oalgpu_context *ctx, uint32_t slot, int32_t target_slot);
+int  oalgpu_slot_target(oalgpu_context *ctx, uint32_t slot, int32_t *target_slot);
+int  oalgpu_slot_order(const int32_t *targets, uint32_t num_slots, uint32_t *order, uint32_t *depth);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -180,6 +180,10 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     c->slotConv.assign(desc->num_slots, nullptr);
     c->slotReverb.assign(desc->num_slots, nullptr);
     c->slotEffect.assign(desc->num_slots, nullptr);
+    c->slotTarget.assign(desc->num_slots, -1);
+    c->slotDepth.assign(desc->num_slots, 0u);
+    c->slotOrder.resize(desc->num_slots);
+    for(uint32_t i = 0; i < desc->num_slots; ++i) c->slotOrder[i] = i;
     HIP_TRY(c->reverbTicket.alloc(1)); HIP_TRY(c->reverbTicket.zero());
     uint32_t vpg = desc->voices_per_group;
     if(vpg == 0)
@@ -333,43 +337,63 @@ int AllocStreamRows(oalgpu_context *c)
     return OALGPU_OK;
 }
 
-static const float *SlotWetBus(const DeviceLayout &L, uint32_t slot) { return L.bus + BusWetOffset(L) + size_t{slot} * L.wetChannels * kLine; }
-// EffectState::process of every slot that has an effect attached (alc/alu.cpp:2209-2257): from
-// channel 0 of the slot's wet bus into the dry lines, on stream `s`, after the buses are final.
+static float *SlotWetBus(const DeviceLayout &L, uint32_t slot) { return L.bus + BusWetOffset(L) + size_t{slot} * L.wetChannels * kLine; }
+// EffectTarget of a slot (alc/alu.cpp:627-632): its target slot's wet bus, or the device's lines (dry, then real)
+static float *SlotDestination(const oalgpu_context *c, uint32_t slot)
+{
+    const int32_t target = c->slotTarget[slot];
+    return target >= 0 ? SlotWetBus(c->L, uint32_t(target)) : c->L.bus;
+}
+// EffectState::process of every slot that has an effect attached (alc/alu.cpp:2209-2257): from the slot's wet bus into its
+// destination, on stream `s`, after the buses are final.  The slots go by descending depth (c->slotOrder, host/slot_order.cpp:
+// a slot in front of the slot it targets, alu.cpp:2220-2249), so a wet bus has everything its feeders add before the slot's own
+// effects read it; everything is launched on `s`, whose order is the order of the sums.  Without targets there is one depth
+// and the order is the slot index.
 static int RunEffects(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
 {
     const DeviceLayout &L = c->L;
-    for(uint32_t slot = 0; slot < L.numSlots; ++slot)
+    for(uint32_t first = 0; first < L.numSlots; )
     {
-        const float *wet = SlotWetBus(L, slot);
-        if(oalgpu_convolution *conv = c->slotConv[slot])
+        const uint32_t depth = c->slotDepth[c->slotOrder[first]];
+        uint32_t last = first;
+        while(last < L.numSlots && c->slotDepth[c->slotOrder[last]] == depth) ++last;
+        for(uint32_t i = first; i < last; ++i)
         {
-            if(int rc = oalgpu_convolution_process_device(conv, s, wet, L.bus, samples_to_do)) return rc;
+            const uint32_t slot = c->slotOrder[i];
+            const float *wet = SlotWetBus(L, slot);
+            if(oalgpu_convolution *conv = c->slotConv[slot])
+            {
+                if(int rc = oalgpu_convolution_process_device(conv, s, wet, SlotDestination(c, slot), samples_to_do)) return rc;
+            }
+            if(oalgpu_effect *fx = c->slotEffect[slot])
+            {
+                if(int rc = oalgpu_effect_process_device(fx, s, wet, SlotDestination(c, slot), samples_to_do)) return rc;
+            }
         }
-        if(oalgpu_effect *fx = c->slotEffect[slot])
+        // the EAX reverbs of the depth's slots: one launch, instances side by side, mix-out in slot order
+        oalgpu_reverb *revs[kRvBatchMax];
+        const float *wets[kRvBatchMax];
+        float *outs[kRvBatchMax];
+        uint32_t count = 0;
+        auto flush = [&]() -> int
         {
-            if(int rc = oalgpu_effect_process_device(fx, s, wet, L.bus, samples_to_do)) return rc;
+            if(!count) return OALGPU_OK;
+            const int rc = oalgpu_reverb_process_batch_device(revs, wets, count, outs, samples_to_do, s, c->reverbTicket.p);
+            count = 0;
+            return rc;
+        };
+        for(uint32_t i = first; i < last; ++i)
+        {
+            const uint32_t slot = c->slotOrder[i];
+            if(!c->slotReverb[slot]) continue;
+            revs[count] = c->slotReverb[slot];
+            wets[count] = SlotWetBus(L, slot);
+            outs[count] = SlotDestination(c, slot);
+            if(++count == kRvBatchMax) { if(int rc = flush()) return rc; }
         }
+        if(int rc = flush()) return rc;
+        first = last;
     }
-    // the EAX reverbs of all slots: one launch, instances side by side, mix-out in slot order
-    oalgpu_reverb *revs[kRvBatchMax];
-    const float *wets[kRvBatchMax];
-    uint32_t count = 0;
-    auto flush = [&]() -> int
-    {
-        if(!count) return OALGPU_OK;
-        const int rc = oalgpu_reverb_process_batch_device(revs, wets, count, L.bus, samples_to_do, s, c->reverbTicket.p);
-        count = 0;
-        return rc;
-    };
-    for(uint32_t slot = 0; slot < L.numSlots; ++slot)
-    {
-        if(!c->slotReverb[slot]) continue;
-        revs[count] = c->slotReverb[slot];
-        wets[count] = SlotWetBus(L, slot);
-        if(++count == kRvBatchMax) { if(int rc = flush()) return rc; }
-    }
-    if(int rc = flush()) return rc;
     return OALGPU_OK;
 }
 
@@ -1169,7 +1193,9 @@ int oalgpu_debug_wave_times(oalgpu_context *c, unsigned long long *out, uint32_t
 int oalgpu_slot_set_convolution(oalgpu_context *c, uint32_t slot, oalgpu_convolution *conv)
 {
     if(!c || slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_convolution: bad slot");
-    if(conv && ConvOutLines(conv) > c->L.numDry)
+    if(conv && c->slotTarget[slot] >= 0 && ConvOutLines(conv) > c->L.wetChannels)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_convolution: the effect mixes into more lines than the wet bus of the slot's target has");
+    if(conv && c->slotTarget[slot] < 0 && ConvOutLines(conv) > c->L.numDry)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_convolution: the effect mixes into more lines than the context has dry lines");
     if(int rc = oalgpu_sync(c)) return rc;
     c->slotConv[slot] = conv;
@@ -1242,7 +1268,8 @@ int oalgpu_slot_set_effect(oalgpu_context *c, uint32_t slot, oalgpu_effect *fx)
 {
     if(!c || slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_effect: bad slot");
     // (a dedicated effect may address the real output lines, which follow the dry lines in the bus block)
-    if(fx && (EffectOutLines(fx) > c->L.numDry + c->L.numReal || EffectInChannels(fx) > c->L.wetChannels))
+    // (on a slot with a target: the target's wet bus)
+    if(fx && (EffectOutLines(fx) > (c->slotTarget[slot] >= 0 ? c->L.wetChannels : c->L.numDry + c->L.numReal) || EffectInChannels(fx) > c->L.wetChannels))
         return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_effect: the effect's lines do not fit the context's buses");
     if(int rc = oalgpu_sync(c)) return rc;
     c->slotEffect[slot] = fx;
@@ -1254,12 +1281,53 @@ int oalgpu_slot_set_reverb(oalgpu_context *c, uint32_t slot, oalgpu_reverb *rev)
     if(!c || slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: bad slot");
     if(rev && c->L.wetChannels < 4)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: the reverb reads a 4-line B-Format wet bus");
-    if(rev && ReverbOutLines(rev) > c->L.numDry)
+    if(rev && c->slotTarget[slot] >= 0 && ReverbOutLines(rev) > c->L.wetChannels)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: the effect mixes into more lines than the wet bus of the slot's target has");
+    if(rev && c->slotTarget[slot] < 0 && ReverbOutLines(rev) > c->L.numDry)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: the effect mixes into more lines than the context has dry lines");
     if(int rc = oalgpu_sync(c)) return rc;
     if(rev) { if(int rc = oalgpu_reverb_set_math_mode(rev, c->exact ? OALGPU_MATH_EXACT : OALGPU_MATH_FAST)) return rc; }
     c->slotReverb[slot] = rev;
     return RebalanceWaveGroups(c);
+}
+
+/* ---- effect slot targets: AL_EFFECTSLOT_TARGET_SOFT (al/auxeffectslot.cpp:504-520; alc/alu.cpp:627-632, :2220-2249) ---- */
+int oalgpu_slot_order(const int32_t *targets, uint32_t num_slots, uint32_t *order, uint32_t *depth)
+{
+    if(num_slots && (!targets || !order)) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_order: null argument");
+    if(!SlotOrder(targets, num_slots, order, depth))
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_order: a target out of range, a slot that targets itself, or a cycle");
+    return OALGPU_OK;
+}
+
+int oalgpu_slot_set_target(oalgpu_context *c, uint32_t slot, int32_t target_slot)
+{
+    const std::string w = "oalgpu_slot_set_target: ";
+    if(!c) return Fail(OALGPU_ERR_INVALID, w + "null context");
+    if(slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, w + "bad slot");
+    if(target_slot < -1 || target_slot >= int32_t(c->L.numSlots)) return Fail(OALGPU_ERR_INVALID, w + "the target is out of range (-1 .. num_slots - 1)");
+    if(target_slot == int32_t(slot)) return Fail(OALGPU_ERR_INVALID, w + "a slot cannot target itself");
+    std::vector<int32_t> targets = c->slotTarget;
+    targets[slot] = target_slot;
+    std::vector<uint32_t> order(c->L.numSlots), depth(c->L.numSlots);
+    if(!SlotOrder(targets.data(), c->L.numSlots, order.data(), depth.data()))
+        return Fail(OALGPU_ERR_INVALID, w + "the target would close a cycle");
+    if(target_slot >= 0 && (ConvOutLines(c->slotConv[slot]) > c->L.wetChannels || EffectOutLines(c->slotEffect[slot]) > c->L.wetChannels
+        || ReverbOutLines(c->slotReverb[slot]) > c->L.wetChannels))
+        return Fail(OALGPU_ERR_INVALID, w + "what is attached to the slot mixes into more lines than the target's wet bus has");
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->slotTarget.swap(targets);
+    c->slotOrder.swap(order);
+    c->slotDepth.swap(depth);
+    return OALGPU_OK;
+}
+
+int oalgpu_slot_target(oalgpu_context *c, uint32_t slot, int32_t *target_slot)
+{
+    if(!c || !target_slot) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_target: null argument");
+    if(slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_target: bad slot");
+    *target_slot = c->slotTarget[slot];
+    return OALGPU_OK;
 }
 
 const char *oalgpu_voice_kernel_name(oalgpu_context *c)

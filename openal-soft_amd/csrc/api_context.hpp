@@ -33,6 +33,7 @@
 #include "../host/mhr.hpp"
 #include "../host/hrtf_build.hpp"
 #include "../host/params.hpp"
+#include "../host/slot_order.hpp"
 #include "../host/tables.hpp"
 #include "api_util.hpp"
 #include "kernels.hpp"
@@ -158,6 +159,11 @@ struct oalgpu_context {
     std::vector<oalgpu_reverb*> slotReverb;      // per effect slot: attached EAX reverb (not owned)
     std::vector<oalgpu_effect*> slotEffect;      // per effect slot: equalizer / modulator / echo / dedicated (not owned)
     DevBuf<uint32_t> reverbTicket;               // mix-out order word of a reverb batch launch
+    // effect slot targets (oalgpu_slot_set_target: AL_EFFECTSLOT_TARGET_SOFT, alc/alu.cpp:627-632 and :2220-2249): slot -> the slot
+    // whose wet bus its effects add into (-1: the device's lines), and what host/slot_order.cpp makes of the graph -- recomputed
+    // when a target changes, read by RunEffects
+    std::vector<int32_t> slotTarget;
+    std::vector<uint32_t> slotOrder, slotDepth;
 
     DevBuf<float> tables;
     DevBuf<BufferItem> buffers;

@@ -231,9 +231,9 @@ static int PrepareBlock(oalgpu_reverb *r, const float *wet_in_dev, float *out_li
 }
 
 int oalgpu_reverb_process_batch_device(oalgpu_reverb *const *revs, const float *const *wet_in_dev, uint32_t count,
-    float *out_lines_dev, uint32_t n, void *hip_stream, uint32_t *ticket_dev)
+    float *const *out_lines_dev, uint32_t n, void *hip_stream, uint32_t *ticket_dev)
 {
-    if(!revs || !wet_in_dev || count == 0 || count > kRvBatchMax || (count > 1 && !ticket_dev))
+    if(!revs || !wet_in_dev || !out_lines_dev || count == 0 || count > kRvBatchMax || (count > 1 && !ticket_dev))
         return Fail(OALGPU_ERR_INVALID, "oalgpu_reverb_process_batch: bad arguments");
     RvBatch B{};
     B.count = count;
@@ -242,7 +242,7 @@ int oalgpu_reverb_process_batch_device(oalgpu_reverb *const *revs, const float *
     {
         if(!revs[i]) return Fail(OALGPU_ERR_INVALID, "oalgpu_reverb_process_batch: null instance");
         revs[i]->stream = static_cast<hipStream_t>(hip_stream);
-        if(int rc = PrepareBlock(revs[i], wet_in_dev[i], out_lines_dev, n, &B.r[i])) return rc;
+        if(int rc = PrepareBlock(revs[i], wet_in_dev[i], out_lines_dev[i], n, &B.r[i])) return rc;
     }
     LaunchReverbBatch(static_cast<hipStream_t>(hip_stream), B);
     HIP_TRY(hipGetLastError());

@@ -64,7 +64,8 @@ void LaunchReverbInstall(hipStream_t s, oalgpu_reverb_pipeline *dst, const oalgp
 
 } // namespace oalgpu
 
-// api.hip: process `count` reverbs (<= kRvBatchMax) that share `out_lines_dev` and a stream as one
-// launch; `ticket_dev` is a zeroed device word owned by the caller
+// api.hip: process `count` reverbs (<= kRvBatchMax) that share a stream as one launch, instance i adding into
+// out_lines_dev[i] (the same block for the instances of slots with the same destination; a slot with a target: that
+// slot's wet bus); `ticket_dev` is a zeroed device word owned by the caller
 int oalgpu_reverb_process_batch_device(oalgpu_reverb *const *revs, const float *const *wet_in_dev, uint32_t count,
-    float *out_lines_dev, uint32_t n, void *hip_stream, uint32_t *ticket_dev);
+    float *const *out_lines_dev, uint32_t n, void *hip_stream, uint32_t *ticket_dev);

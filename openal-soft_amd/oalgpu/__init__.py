@@ -258,6 +258,19 @@ def crossfeed_constants(level, rate):
     return out
 
 
+def slot_order(targets):
+    """The processing order of effect slots with targets[i] = the slot that slot i feeds (-1: the device's lines): ->
+    (order uint32[n], depth uint32[n]).  Host only (oalgpu_slot_order)."""
+    t = np.ascontiguousarray(targets, np.int32)
+    order = np.zeros(t.size, np.uint32)
+    depth = np.zeros(t.size, np.uint32)
+    u32 = C.POINTER(C.c_uint32)
+    lib.oalgpu_slot_order.argtypes = [C.POINTER(C.c_int32), C.c_uint32, u32, u32]
+    check(lib.oalgpu_slot_order(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, order.ctypes.data_as(u32), depth.ctypes.data_as(u32)),
+          "oalgpu_slot_order")
+    return order, depth
+
+
 class StabilizerParams(C.Structure):
     """oalgpu_stabilizer_params"""
     _fields_ = [("left", C.c_uint32), ("right", C.c_uint32), ("center", C.c_uint32), ("xover_norm", C.c_float)]
@@ -818,6 +831,17 @@ class Scene:
     def set_slot_reverb(self, slot, rev):
         lib.oalgpu_slot_set_reverb.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         check(lib.oalgpu_slot_set_reverb(self.h, slot, rev.h if rev is not None else None))
+
+    def set_slot_target(self, slot, target):
+        """everything attached to `slot` adds into the wet bus of slot `target` (None or -1: the device's lines)"""
+        lib.oalgpu_slot_set_target.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
+        check(lib.oalgpu_slot_set_target(self.h, slot, -1 if target is None else target), "oalgpu_slot_set_target")
+
+    def slot_target(self, slot):
+        lib.oalgpu_slot_target.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]
+        t = C.c_int32(0)
+        check(lib.oalgpu_slot_target(self.h, slot, C.byref(t)), "oalgpu_slot_target")
+        return t.value
 
     def mix(self, samples_to_do=BUFFER_LINE, post_process=False):
         check(lib.oalgpu_mix_update(self.h, samples_to_do, 1 if post_process else 0),
