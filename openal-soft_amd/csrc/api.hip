@@ -2,7 +2,7 @@
 // HBM allocation/upload, parameter preparation that the reference does with libm on its mixer
 // thread (resampler state, biquad design), and kernel launches on the context's stream.
 // No CPU fallback exists anywhere in this file: without a HIP device every entry point fails.
-// (The rest of the C-ABI: api_comm.hip, api_percall.hip, api_hrtf.hip, api_voices.hip, api_output.hip, api_poststage.hip, api_callback.hip; shared: api_context.hpp.)
+// (The rest of the C-ABI: api_comm.hip, api_percall.hip, api_hrtf.hip, api_buffers.hip, api_voices.hip, api_output.hip, api_poststage.hip, api_callback.hip; shared: api_context.hpp.)
 #include "api_context.hpp"
 namespace oalgpu {
 
@@ -114,19 +114,13 @@ int FlushInits(oalgpu_context *c)
 {
     if(c->initPending.empty()) return OALGPU_OK;
     const size_t n = c->initPending.size();
-    if(c->initDev.n < n) HIP_TRY(c->initDev.alloc(n));
-    HIP_TRY(hipMemcpyAsync(c->initDev.p, c->initPending.data(), n * sizeof(VoiceInitRecord), hipMemcpyHostToDevice, c->stream));
+    if(int rc = StageRecords(c->stream, c->initDev, c->initPending.data(), n)) return rc;
     LaunchInitVoices(c->stream, c->L, c->initDev.p, uint32_t(n));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));   // the host vector is reused
+    HIP_TRY(hipStreamSynchronize(c->stream));
     c->initPending.clear();
     return OALGPU_OK;
 }
-
-
-
-
-
 
 static void SetRowsGroups(oalgpu_context *c);      // (voice_rows.hip's grid; defined beside RebalanceWaveGroups)
 
@@ -214,12 +208,7 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     L.tables = c->tables.p;
     HIP_TRY(c->buffers.alloc(std::max<uint32_t>(desc->max_buffers, 1u))); HIP_TRY(c->buffers.zero());
     L.buffers = c->buffers.p;
-    c->bufferData.assign(std::max<uint32_t>(desc->max_buffers, 1u), nullptr);
-    c->bufferLoopLen.assign(std::max<uint32_t>(desc->max_buffers, 1u), 0u);
-    c->bufHost.assign(std::max<uint32_t>(desc->max_buffers, 1u), oalgpu_context::BufHost{});
-    c->voiceHead.assign(std::max<uint32_t>(desc->max_voices, 1u), -1);
-    c->queueDoneKnown.assign(std::max<uint32_t>(desc->max_voices, 1u), 0u);
-    c->queueUnqueued.assign(std::max<uint32_t>(desc->max_voices, 1u), 0u);
+    c->buf.reset(desc->max_buffers, desc->max_voices);
     c->cbOfVoice.assign(std::max<uint32_t>(desc->max_voices, 1u), -1);
 
     const size_t nv = desc->max_voices;

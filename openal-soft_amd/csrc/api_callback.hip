@@ -62,7 +62,7 @@ int ServiceCallbacks(oalgpu_context *c, uint32_t samplesToDo)
         if(bytes)
         {
             std::memcpy(cb.pinned[slot], cb.data.data(), bytes);
-            HIP_TRY(hipMemcpyAsync(c->bufferData[size_t(cb.buffer)], cb.pinned[slot], bytes, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->buf.at(cb.buffer).storage, cb.pinned[slot], bytes, hipMemcpyHostToDevice, c->stream));
         }
         HIP_TRY(hipEventRecord(cb.copied[slot], c->stream));
         LaunchSetVoiceWindow(c->stream, c->L, cb.voice, cb.buffer, cb.numBlocks, int32_t(cb.blockOffset));
@@ -96,12 +96,9 @@ int ServiceCallbacks(oalgpu_context *c, uint32_t samplesToDo)
     return OALGPU_OK;
 }
 
-
-
 int oalgpu_voice_init_callback(oalgpu_context *c, uint32_t voice, int fmt_type, uint32_t position_frac,
     oalgpu_callback_fn fn, void *userptr)
 {
-    static const uint32_t bytesPer[7] = {1, 2, 4, 4, 8, 1, 1};
     if(!c || !fn || voice >= c->L.numVoices || fmt_type < 0 || fmt_type > OALGPU_FMT_ALAW || position_frac >= kFracOne)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_init_callback: bad arguments");
     if(c->comm) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_init_callback: not on a sharded context");
@@ -114,30 +111,30 @@ int oalgpu_voice_init_callback(oalgpu_context *c, uint32_t voice, int fmt_type, 
         RetireCallbackVoice(c, voice);
     }
     const uint32_t capacityFrames = uint32_t(kLine + 256) * 10u + uint32_t(kMaxEdge);      // MixerLineSize*MaxPitch + MaxResamplerEdge, al/buffer.cpp:474
-    const size_t nbytes = size_t{capacityFrames} * bytesPer[fmt_type];
-    // a retired entry's buffer-table slot, device buffer, pinned staging and events serve the new source
+    const size_t nbytes = size_t{capacityFrames} * kSourceBytesPer[fmt_type];
+    // a retired entry's pinned staging and events serve the new source; its handle and device buffer go back to the table
     int32_t reuse = -1;
     for(size_t j = 0; j < c->cbVoices.size(); ++j)
         if(c->cbVoices[j].retired) { reuse = int32_t(j); break; }
-    if(reuse < 0 && c->freeBuffers.empty() && c->numBuffers >= c->desc.max_buffers) return Fail(OALGPU_ERR_CAPACITY, "buffer table full");
     oalgpu_context::CbVoice fresh;
     oalgpu_context::CbVoice &cb = reuse >= 0 ? c->cbVoices[size_t(reuse)] : fresh;
     if(reuse >= 0)
     {
         if(int rc = oalgpu_sync(c)) return rc;                     // nothing in flight reads the old source's data any more
+        if(c->buf.usable(cb.buffer)) FreeStorage(c->buf.release(cb.buffer));
+        cb.buffer = -1;
         if(cb.allocBytes < nbytes)
         {   // a wider sample type than the entry was made for
-            (void)hipFree(c->bufferData[size_t(cb.buffer)]); c->bufferData[size_t(cb.buffer)] = nullptr;
             for(int k = 0; k < 2; ++k) { (void)hipHostFree(cb.pinned[k]); cb.pinned[k] = nullptr; }
             cb.allocBytes = 0;
         }
     }
-    struct Undo {       // what a failure below must not leave behind
-        oalgpu_context *c; oalgpu_context::CbVoice *cb; void *dev{nullptr}; bool armed{true};
+    if(c->buf.full()) return Fail(OALGPU_ERR_CAPACITY, "buffer table full");
+    struct Undo {       // what a failure below must not leave behind of the entry's own: pinned staging and events
+        oalgpu_context::CbVoice *cb; bool armed{true};
         ~Undo()
         {
             if(!armed) return;
-            if(dev) (void)hipFree(dev);
             for(int k = 0; k < 2; ++k)
             {
                 if(cb->pinned[k]) { (void)hipHostFree(cb->pinned[k]); cb->pinned[k] = nullptr; }
@@ -145,35 +142,29 @@ int oalgpu_voice_init_callback(oalgpu_context *c, uint32_t voice, int fmt_type, 
             }
             cb->allocBytes = 0;
         }
-    } undo{c, &cb};
-    void *dev = cb.allocBytes ? c->bufferData[size_t(cb.buffer)] : nullptr;
-    if(!cb.allocBytes)
+    } undo{&cb};
+    for(int k = 0; k < 2 && !cb.allocBytes; ++k)
     {
-        HIP_TRY(hipMalloc(&dev, nbytes + 16));
-        undo.dev = dev;
-        for(int k = 0; k < 2; ++k)
-        {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&cb.pinned[k]), nbytes, hipHostMallocDefault));
-            if(!cb.copied[k]) HIP_TRY(hipEventCreateWithFlags(&cb.copied[k], hipEventDisableTiming));
-        }
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&cb.pinned[k]), nbytes, hipHostMallocDefault));
+        if(!cb.copied[k]) HIP_TRY(hipEventCreateWithFlags(&cb.copied[k], hipEventDisableTiming));
     }
-    HIP_TRY(hipMemset(dev, 0, nbytes + 16));
     for(int k = 0; k < 2; ++k) HIP_TRY(hipEventRecord(cb.copied[k], c->stream));
-    uint32_t h = reuse >= 0 ? uint32_t(cb.buffer) : 0u;
-    if(reuse < 0) { if(int rc = AllocBufferHandle(c, &h)) return rc; }       // (the storage is the library's own: never released by the host)
-    // one frame long until the first update hands the voice its window (a static buffer has at least one)
-    BufferItem item{dev, fmt_type, 1u, 1u, 0u, 0u, 0};
-    HIP_TRY(hipMemcpy(c->buffers.p + h, &item, sizeof(item), hipMemcpyHostToDevice));
+    void *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, nbytes + 16));
+    const hipError_t e = hipMemset(dev, 0, nbytes + 16);
+    if(e != hipSuccess) { (void)hipFree(dev); return Fail(OALGPU_ERR_HIP, hipGetErrorString(e)); }
+    // one frame long until the first update hands the voice its window (a static buffer has at least one); the storage is the
+    // library's own, never released by the host, so the voice slot's hold stays where it was
+    const int h = RegisterBuffer(c, dev, BufferItem{dev, fmt_type, 1u, 1u, 0u, 0u, 0}, 0u, -1);
+    if(h < 0) return h;
+    PendStart(c, VoiceInitRecord{voice, h, 0, 0, position_frac, 0});
     undo.armed = false;
-    c->bufferData[h] = dev;
-    c->bufferLoopLen[h] = 0u;
     cb.voice = voice; cb.fn = fn; cb.user = userptr; cb.buffer = int32_t(h);
-    cb.frameBytes = bytesPer[fmt_type]; cb.capacityFrames = capacityFrames;
-    if(!cb.allocBytes) cb.allocBytes = nbytes;
+    cb.frameBytes = kSourceBytesPer[fmt_type]; cb.capacityFrames = capacityFrames;
+    cb.allocBytes = std::max(cb.allocBytes, nbytes);
     cb.data.assign(nbytes, 0);
     cb.numBlocks = 0; cb.blockOffset = 0; cb.stopped = false; cb.position = 0; cb.frac = position_frac; cb.step = 0;
     cb.state = OALGPU_VOICE_PLAYING; cb.hasBuffer = true; cb.slot = 0; cb.retired = false;
-    c->initPending.push_back(VoiceInitRecord{voice, int32_t(h), 0, 0, position_frac, 0});
     if(reuse >= 0) c->cbOfVoice[voice] = reuse;
     else
     {
@@ -193,5 +184,4 @@ int oalgpu_voice_callback_state(oalgpu_context *c, uint32_t voice, oalgpu_callba
     out->stopped = cb.stopped ? 1 : 0; out->play_state = cb.state; out->has_buffer = cb.hasBuffer ? 1 : 0;
     return OALGPU_OK;
 }
-
 

@@ -1,6 +1,6 @@
 // The device context and what the C-ABI translation units share (api.hip: context life, the update, slots; api_comm.hip: the
-// sharded update's transports; api_percall.hip: the per-call operators; api_hrtf.hip: HRTF data sets; api_voices.hip: buffers, voices,
-// parameters; api_output.hip: what comes back; api_poststage.hip: what is installed and run behind the buses; api_callback.hip:
+// sharded update's transports; api_percall.hip: the per-call operators; api_hrtf.hip: HRTF data sets; api_buffers.hip: buffer handles;
+// api_voices.hip: voices, parameters; api_output.hip: what comes back; api_poststage.hip: what is installed and run behind the buses; api_callback.hip:
 // callback sources).  Host logic only; no CPU fallback anywhere.
 #pragma once
 #include "../../include/oalgpu.h"
@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "../host/buffer_table.hpp"
 #include "../host/mhr.hpp"
 #include "../host/hrtf_build.hpp"
 #include "../host/params.hpp"
@@ -169,17 +170,9 @@ struct oalgpu_context {
     DevBuf<BufferItem> buffers;
     DevBuf<uint32_t> startDelay;           // [voice] samples until a delayed voice starts
     DevBuf<uint32_t> queueDone;            // [voice] buffers a streaming voice has played through
-    std::vector<void*> bufferData;
-    std::vector<uint32_t> bufferLoopLen;   // loop_end - loop_start of every registered buffer (0: cannot loop)
-    uint32_t numBuffers{0};                // handles handed out so far (released ones are reused: freeBuffers)
-    // The lifetime of a buffer handle (oalgpu_buffer_release): a handle is freed -- its HBM copy, and the handle for reuse -- when
-    // the host has released it AND nothing refers to it any more: no voice slot that was initialised on it (voiceHead: cleared when
-    // the slot is initialised again or set to Stopped), no live buffer whose queue link points at it, no channel view of it.
-    struct BufHost { bool live{false}, released{false}; int32_t parent{-1}, next{-1}; uint32_t refs{0}; };
-    std::vector<BufHost> bufHost;
-    std::vector<uint32_t> freeBuffers;
-    std::vector<int32_t> voiceHead;        // [voice] the buffer the slot was initialised on (a queue: its first), -1: none
-    std::vector<uint32_t> queueDoneKnown, queueUnqueued;   // [voice] AsyncBufferComplete counts the host has read back / given up (oalgpu_voice_queue_unqueue)
+    // the host's record of every buffer handle (its HBM copy, loop length, who holds it) and of what each voice slot holds:
+    // host/buffer_table.hpp has the lifetime rules (oalgpu_buffer_release), api_buffers.hip frees what they hand back
+    BufferTable buf;
     DevBuf<VoiceCtl> ctl;
     DevBuf<float> prev, hrtfOld, hrtfTgt, hist, gainCur, gainTgt, sendCur, sendTgt;
     DevBuf<BiquadSlot> dfilt, sfilt;
@@ -337,7 +330,7 @@ struct oalgpu_context {
 
     ~oalgpu_context()
     {
-        for(void *p : bufferData) if(p) (void)hipFree(p);
+        for(int h = 0; buf.inRange(h); ++h) (void)hipFree(buf.at(h).storage);    // (what the table still holds)
         for(uint32_t k = 0; k < kIoSlots; ++k)
         {
             if(panHost[k]) (void)(panInBar ? hipFree(panHost[k]) : hipHostFree(panHost[k]));
@@ -413,7 +406,14 @@ bool RingEligible(const oalgpu_context *c);                        // api_output
 inline float *RealOut(const oalgpu_context *c) { return c->L.numReal ? c->L.bus + size_t{c->L.numDry} * kLine : c->L.bus; }
 inline uint32_t RealOutLines(const oalgpu_context *c) { return c->L.numReal ? c->L.numReal : c->L.numDry; }
 bool HostStoresReachDevice(oalgpu_context *c);                     // api_voices.hip
-int AllocBufferHandle(oalgpu_context *c, uint32_t *out);           // api_voices.hip
+// buffer handles (api_buffers.hip): the tail of every registration -> the handle, or an error; the storage a drop handed back
+int RegisterBuffer(oalgpu_context *c, void *storage, BufferItem item, uint32_t loopLen, int parent);
+void FreeStorage(const std::vector<void*> &freed);
+// voices (api_voices.hip).  What an entry point that looks at the voices starts with, like BeginSetter: `argsOk` false is
+// `who`'s error; then UseCtx, the deferred starts (FlushInits) and, with `sync`, oalgpu_sync.  PendStart: a deferred start.
+inline bool VoiceOk(const oalgpu_context *c, uint32_t voice) { return c && voice < c->L.numVoices; }
+int BeginVoiceCall(oalgpu_context *c, bool argsOk = true, const char *who = "", bool sync = false);
+void PendStart(oalgpu_context *c, const VoiceInitRecord &rec);
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip
 int ServiceCallbacks(oalgpu_context *c, uint32_t samplesToDo);     // api_callback.hip
 int CommReduceBus(oalgpu_context *c, hipStream_t s);               // api_comm.hip

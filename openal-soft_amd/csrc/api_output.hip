@@ -97,8 +97,7 @@ int oalgpu_output_wait(oalgpu_context *c, uint32_t ticket, float *out, size_t ou
 int oalgpu_voice_events_async(oalgpu_context *c, uint32_t *ticket)
 {
     if(!c || !ticket) return Fail(OALGPU_ERR_INVALID, "null argument");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     constexpr uint32_t slots = oalgpu_context::kIoSlots;
     if(!c->evHost[0])
     {
@@ -140,7 +139,7 @@ int oalgpu_voice_events_wait(oalgpu_context *c, uint32_t ticket, oalgpu_voice_ev
     {
         const uint32_t *e = h + 4u + size_t{i} * 8u;
         out[i] = oalgpu_voice_event{e[0], int32_t(e[1]), int32_t(e[2]) >= 0 ? 1 : 0, int32_t(e[2]), e[3], int32_t(e[4]), e[5], int32_t(e[6])};
-        if(e[0] < c->L.numVoices) c->queueDoneKnown[e[0]] = e[3];      // (what oalgpu_voice_queue_unqueue checks against)
+        if(e[0] < c->L.numVoices) c->buf.noteQueueDone(e[0], e[3]);      // (what oalgpu_voice_queue_unqueue checks against)
     }
     return OALGPU_OK;
 }
@@ -245,10 +244,7 @@ int oalgpu_bus_device_ptr(oalgpu_context *c, void **ptr, size_t *nfloats, void *
 
 int oalgpu_voice_readback(oalgpu_context *c, uint32_t v, oalgpu_voice_state *out)
 {
-    if(!c || !out || v >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_readback: bad arguments");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
-    if(int rc = oalgpu_sync(c)) return rc;
+    if(int rc = BeginVoiceCall(c, VoiceOk(c, v) && out, "oalgpu_voice_readback", true)) return rc;
     const DeviceLayout &L = c->L;
     std::memset(out, 0, sizeof(*out));
     VoiceCtl ctl;
@@ -285,9 +281,7 @@ int oalgpu_voices_readback(oalgpu_context *c, const uint32_t *voices, size_t cou
 {
     if(!c || !voices || !out) return Fail(OALGPU_ERR_INVALID, "oalgpu_voices_readback: null argument");
     if(count == 0) return OALGPU_OK;
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
-    if(int rc = oalgpu_sync(c)) return rc;
+    if(int rc = BeginVoiceCall(c, true, "", true)) return rc;
     // one copy of the control lines the voices span (128 bytes each), not one round trip per voice
     uint32_t lo = 0xffffffffu, hi = 0u;
     for(size_t i = 0; i < count; ++i)
@@ -313,7 +307,7 @@ int oalgpu_voices_readback(oalgpu_context *c, const uint32_t *voices, size_t cou
         for(size_t i = 0; i < count; ++i)
         {
             out[i].buffers_done = c->doneHost[voices[i] - lo];
-            c->queueDoneKnown[voices[i]] = out[i].buffers_done;
+            c->buf.noteQueueDone(voices[i], out[i].buffers_done);
         }
     }
     return OALGPU_OK;

@@ -49,4 +49,19 @@ struct DevBuf {
     hipError_t alloc_zero(size_t count) { const hipError_t err = alloc(count); return err != hipSuccess ? err : zero(); }
 };
 
+// Staged records: the device staging grows if it is smaller, and `count` records are copied into it on `stream`.  One rule for
+// every user (FlushInits, oalgpu_voice_set_params, _set_hrtf_targets, _set_pan): the caller launches what reads the staging,
+// THEN waits for the stream -- host memory and staging are both free when the entry point returns, and nobody waits in front
+// of the copy.
+template<typename T>
+int StageRecords(hipStream_t stream, DevBuf<T> &dev, const T *host, size_t count)
+{
+    if(dev.n < count) HIP_TRY(dev.alloc(count));
+    HIP_TRY(hipMemcpyAsync(dev.p, host, count * sizeof(T), hipMemcpyHostToDevice, stream));
+    return OALGPU_OK;
+}
+
+// bytes per sample of a source sample type (oalgpu_sample_type; the output types of api_output.hip / api_percall.hip are another enum)
+constexpr uint32_t kSourceBytesPer[7] = {1, 2, 4, 4, 8, 1, 1};
+
 } // namespace oalgpu

@@ -1,172 +1,70 @@
-// Buffers, voices, parameters: handles and their lifetime, voice starts and queues, parameter records and blocks, moves, pan.
+// Voices and their parameters: voice starts and queues, the per-voice setters, parameter records and blocks, moves, pan.
 #include "api_context.hpp"
 
-// ---- buffer handles: allocation, references, release ----
-static bool BufferLive(const oalgpu_context *c, int h) { return h >= 0 && uint32_t(h) < c->numBuffers && c->bufHost[size_t(h)].live; }
-int AllocBufferHandle(oalgpu_context *c, uint32_t *out)
+int BeginVoiceCall(oalgpu_context *c, bool argsOk, const char *who, bool sync)
 {
-    if(!c->freeBuffers.empty()) { *out = c->freeBuffers.back(); c->freeBuffers.pop_back(); }
-    else if(c->numBuffers < c->desc.max_buffers) *out = c->numBuffers++;
-    else return Fail(OALGPU_ERR_CAPACITY, "buffer table full");
-    c->bufHost[*out] = oalgpu_context::BufHost{};
-    c->bufHost[*out].live = true;
-    return OALGPU_OK;
-}
-static void BufferUnref(oalgpu_context *c, int h);
-// (the caller has made sure nothing on the device still reads the buffer: hipFree waits for the device besides)
-static void BufferFreeNow(oalgpu_context *c, int h)
-{
-    auto &b = c->bufHost[size_t(h)];
-    if(c->bufferData[size_t(h)]) { (void)hipFree(c->bufferData[size_t(h)]); c->bufferData[size_t(h)] = nullptr; }
-    const int32_t parent = b.parent, next = b.next;
-    b = oalgpu_context::BufHost{};
-    c->bufferLoopLen[size_t(h)] = 0;
-    c->freeBuffers.push_back(uint32_t(h));
-    if(parent >= 0) BufferUnref(c, parent);
-    if(next >= 0) BufferUnref(c, next);
-}
-static void BufferUnref(oalgpu_context *c, int h)
-{
-    if(h < 0) return;
-    auto &b = c->bufHost[size_t(h)];
-    if(b.refs) --b.refs;
-    if(b.refs == 0 && b.released && b.live) BufferFreeNow(c, h);
-}
-static void SetVoiceHead(oalgpu_context *c, uint32_t voice, int h)
-{
-    const int old = c->voiceHead[voice];
-    c->voiceHead[voice] = h;
-    if(h >= 0) ++c->bufHost[size_t(h)].refs;
-    if(old >= 0) BufferUnref(c, old);
-}
-
-int oalgpu_buffer_release(oalgpu_context *c, int buffer)
-{
-    if(!c || !BufferLive(c, buffer)) return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_release: not a registered buffer");
-    if(c->bufHost[size_t(buffer)].released) return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_release: released before");
+    if(!argsOk) return Fail(OALGPU_ERR_INVALID, std::string(who) + ": bad arguments");
     if(int rc = UseCtx(c)) return rc;
-    for(const auto &cb : c->cbVoices)
-        if(cb.buffer == buffer && !cb.retired) return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_release: a callback source's storage is the library's own");
-    // initialisations that wait for the next update name their buffers: they are on the device before anything is freed
     if(int rc = FlushInits(c)) return rc;
-    auto &b = c->bufHost[size_t(buffer)];
-    b.released = true;
-    if(b.refs == 0) BufferFreeNow(c, buffer);
-    return OALGPU_OK;
+    return sync ? oalgpu_sync(c) : OALGPU_OK;
 }
 
-int oalgpu_buffer_info(oalgpu_context *c, int buffer, int32_t *live, int32_t *release_pending, uint32_t *references)
+// A start waits for the next update or the next entry point that looks at the voices (FlushInits).  A slot has ONE pending
+// start, the last: InitVoicesKernel runs a workgroup per record, and two records of one voice would race for its state.
+void PendStart(oalgpu_context *c, const VoiceInitRecord &rec)
 {
-    if(!c || buffer < 0 || uint32_t(buffer) >= c->bufHost.size()) return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_info: bad handle");
-    const auto &b = c->bufHost[size_t(buffer)];
-    if(live) *live = b.live ? 1 : 0;
-    if(release_pending) *release_pending = (b.live && b.released) ? 1 : 0;
-    if(references) *references = b.refs;
-    return OALGPU_OK;
+    auto &p = c->initPending;
+    p.erase(std::remove_if(p.begin(), p.end(), [&](const VoiceInitRecord &r) { return r.voice == rec.voice; }), p.end());
+    p.push_back(rec);
 }
 
-int oalgpu_buffer_register(oalgpu_context *c, const void *data, int fmt_type, uint32_t frame_step,
-    uint32_t sample_len, uint32_t loop_start, uint32_t loop_end)
-{
-    static const size_t bytesPer[7] = {1, 2, 4, 4, 8, 1, 1};
-    if(!c || !data || fmt_type < 0 || fmt_type > OALGPU_FMT_ALAW || frame_step == 0 || sample_len == 0
-        || loop_end > sample_len || loop_start >= (loop_end ? loop_end : 1u))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_register: bad arguments");
-    if(c->freeBuffers.empty() && c->numBuffers >= c->desc.max_buffers) return Fail(OALGPU_ERR_CAPACITY, "buffer table full");
-    if(int rc = UseCtx(c)) return rc;
-    const size_t nbytes = size_t{sample_len} * frame_step * bytesPer[fmt_type];
-    void *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, nbytes + 16));
-    const hipError_t e = hipMemcpy(dev, data, nbytes, hipMemcpyHostToDevice);
-    if(e != hipSuccess) { (void)hipFree(dev); return Fail(OALGPU_ERR_HIP, hipGetErrorString(e)); }
-    uint32_t h = 0;
-    if(int rc = AllocBufferHandle(c, &h)) { (void)hipFree(dev); return rc; }
-    c->bufferData[h] = dev;
-    c->bufferLoopLen[h] = loop_end > loop_start ? loop_end - loop_start : 0u;
-    BufferItem item{dev, fmt_type, frame_step, sample_len, loop_start, loop_end, 0};
-    HIP_TRY(hipMemcpy(c->buffers.p + h, &item, sizeof(item), hipMemcpyHostToDevice));
-    return int(h);
-}
-
-int oalgpu_voice_init(oalgpu_context *c, uint32_t voice, const oalgpu_voice_desc *d)
-{
-    if(c) { if(int rc = FlushPendingMix(c)) return rc; }
-    // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
-    if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c || !d || voice >= c->L.numVoices || !BufferLive(c, d->buffer) || c->bufHost[size_t(d->buffer)].released
-        || d->position_frac >= kFracOne)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_init: bad arguments");
-    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
-    if(d->looping && c->bufferLoopLen[size_t(d->buffer)] == 0)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_init: a looping voice needs a buffer registered with loop_end > loop_start");
-    RetireCallbackVoice(c, voice);
-    c->initPending.push_back(VoiceInitRecord{voice, d->buffer, d->looping ? 1 : 0, d->position, d->position_frac, 0});
-    if(c->voiceHead[voice] >= 0 && c->bufHost[size_t(c->voiceHead[voice])].released)
-    {   // the slot's old buffer may be freed by this: the device must be through with it (and the initialisation on it first)
-        if(int rc = UseCtx(c)) return rc;
-        if(int rc = FlushInits(c)) return rc;
-    }
-    SetVoiceHead(c, voice, d->buffer);
-    c->queueDoneKnown[voice] = c->queueUnqueued[voice] = 0;
-    return OALGPU_OK;
-}
-
-/* ---- streaming sources: a queue of buffers (VoiceBufferItem::mNext, core/voice.h:85) --------------------
- * oalgpu_buffer_queue_link(buffer, next) is alSourceQueueBuffers' linking (next < 0 ends the queue);
- * oalgpu_voice_init_queue starts a voice that is NOT VoiceFlag::IsStatic on the queue's first buffer:
- * LoadBufferQueue (voice.cpp:563-594) crawls the queue, a looping voice returns to `first_buffer` when it
- * ends, and Voice::mix leaves finished buffers behind (voice.cpp:1182-1194). */
-int oalgpu_buffer_queue_link(oalgpu_context *c, int buffer, int next_buffer)
-{
-    if(!c || !BufferLive(c, buffer) || (next_buffer >= 0 && (!BufferLive(c, next_buffer) || c->bufHost[size_t(next_buffer)].released)))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_queue_link: bad buffer");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = oalgpu_sync(c)) return rc;
-    {   // the link holds its target
-        const int32_t old = c->bufHost[size_t(buffer)].next;
-        c->bufHost[size_t(buffer)].next = next_buffer < 0 ? -1 : next_buffer;
-        if(next_buffer >= 0) ++c->bufHost[size_t(next_buffer)].refs;
-        if(old >= 0) BufferUnref(c, old);
-    }
-    const int32_t next = next_buffer < 0 ? 0 : next_buffer + 1;
-    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(c->buffers.p + buffer) + offsetof(BufferItem, next), &next, sizeof(next),
-        hipMemcpyHostToDevice));
-    return OALGPU_OK;
-}
-
-int oalgpu_voice_init_queue(oalgpu_context *c, uint32_t voice, int first_buffer, int looping, int32_t position,
+/* The one start of oalgpu_voice_init (a static voice) and oalgpu_voice_init_queue (a voice that is NOT VoiceFlag::IsStatic,
+ * on the queue's first buffer: LoadBufferQueue, voice.cpp:563-594, crawls the queue, a looping voice returns to the first
+ * buffer when it ends, and Voice::mix leaves finished buffers behind, voice.cpp:1182-1194).  The slot holds its buffer from
+ * now on and lets go of the one before. */
+static int StartVoice(oalgpu_context *c, const char *who, bool queue, uint32_t voice, int buffer, int looping, int32_t position,
     uint32_t position_frac)
 {
     if(c) { if(int rc = FlushPendingMix(c)) return rc; }
     // (a parameter block that waits for a resident update was applied BEFORE this call: it goes in first, as on the launched path)
     if(c && c->res.pendingBlock) { if(int rc = UseCtx(c)) return rc; }
-    if(!c || voice >= c->L.numVoices || !BufferLive(c, first_buffer) || c->bufHost[size_t(first_buffer)].released || position_frac >= kFracOne)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_init_queue: bad arguments");
+    if(!VoiceOk(c, voice) || !c->buf.usable(buffer) || position_frac >= kFracOne)
+        return Fail(OALGPU_ERR_INVALID, std::string(who) + ": bad arguments");
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
+    if(looping && !queue && c->buf.at(buffer).loopLen == 0)
+        return Fail(OALGPU_ERR_INVALID, std::string(who) + ": a looping voice needs a buffer registered with loop_end > loop_start");
     RetireCallbackVoice(c, voice);
-    c->initPending.push_back(VoiceInitRecord{voice, first_buffer, looping ? 1 : 0, position, position_frac, 1});
-    if(c->voiceHead[voice] >= 0 && c->bufHost[size_t(c->voiceHead[voice])].released)
-    {
+    PendStart(c, VoiceInitRecord{voice, buffer, looping ? 1 : 0, position, position_frac, queue ? 1 : 0});
+    if(c->buf.headReleased(voice))
+    {   // the slot's old buffer may be freed by this: the device must be through with it (and the initialisation on it first)
         if(int rc = UseCtx(c)) return rc;
         if(int rc = FlushInits(c)) return rc;
     }
-    SetVoiceHead(c, voice, first_buffer);
-    c->queueDoneKnown[voice] = c->queueUnqueued[voice] = 0;
+    FreeStorage(c->buf.start(voice, buffer));
     return OALGPU_OK;
+}
+
+int oalgpu_voice_init(oalgpu_context *c, uint32_t voice, const oalgpu_voice_desc *d)
+{
+    const oalgpu_voice_desc none{-1, 0, 0, 0u, 0u};             // (a null description names no buffer)
+    if(!d) d = &none;
+    return StartVoice(c, "oalgpu_voice_init", false, voice, d->buffer, d->looping, d->position, d->position_frac);
+}
+
+int oalgpu_voice_init_queue(oalgpu_context *c, uint32_t voice, int first_buffer, int looping, int32_t position,
+    uint32_t position_frac)
+{
+    return StartVoice(c, "oalgpu_voice_init_queue", true, voice, first_buffer, looping, position, position_frac);
 }
 
 /* where a streaming voice is: its current buffer (-1: the queue ended) and the number of buffers it has
  * played through since it was initialised (what AsyncBufferCompleteEvent counts, voice.cpp:1207-1218) */
 int oalgpu_voice_queue_state(oalgpu_context *c, uint32_t voice, int32_t *current_buffer, uint32_t *buffers_done)
 {
-    if(!c || voice >= c->L.numVoices || !current_buffer || !buffers_done)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_queue_state: bad arguments");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
-    if(int rc = oalgpu_sync(c)) return rc;
+    if(int rc = BeginVoiceCall(c, VoiceOk(c, voice) && current_buffer && buffers_done, "oalgpu_voice_queue_state", true)) return rc;
     HIP_TRY(hipMemcpy(current_buffer, &c->ctl.p[voice].curBuffer, sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(buffers_done, c->queueDone.p + voice, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    c->queueDoneKnown[voice] = *buffers_done;
+    c->buf.noteQueueDone(voice, *buffers_done);
     return OALGPU_OK;
 }
 
@@ -175,54 +73,13 @@ int oalgpu_voice_queue_state(oalgpu_context *c, uint32_t voice, int32_t *current
  * moves on to the buffer behind them, so that a released buffer among them can be freed while the source plays on. */
 int oalgpu_voice_queue_unqueue(oalgpu_context *c, uint32_t voice, uint32_t count)
 {
-    if(!c || voice >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_queue_unqueue: bad arguments");
+    if(!VoiceOk(c, voice)) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_queue_unqueue: bad arguments");
     if(count == 0) return OALGPU_OK;
-    if(c->queueUnqueued[voice] + count > c->queueDoneKnown[voice])
+    if(!c->buf.canUnqueue(voice, count))
         return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_queue_unqueue: more buffers than the voice is known to have played through (read its state back first)");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
-    if(int rc = oalgpu_sync(c)) return rc;
-    int head = c->voiceHead[voice];
-    for(uint32_t i = 0; i < count && head >= 0; ++i) head = c->bufHost[size_t(head)].next;
-    c->queueUnqueued[voice] += count;
-    SetVoiceHead(c, voice, head);
+    if(int rc = BeginVoiceCall(c, true, "", true)) return rc;
+    FreeStorage(c->buf.unqueue(voice, count));
     return OALGPU_OK;
-}
-
-/* IMA4 / MS ADPCM data (FmtIMA4 / FmtMSADPCM, core/buffer_storage.h; LoadSamples, core/voice.cpp:288-484):
- * decoded once, on the GPU, into interleaved 16-bit PCM; the handle then behaves like an OALGPU_FMT_SHORT
- * buffer with frame_step = channels (oalgpu_buffer_channel_view splits a stereo one). */
-int oalgpu_buffer_register_adpcm(oalgpu_context *c, const void *data, int adpcm_type, uint32_t channels,
-    uint32_t samples_per_block, uint32_t sample_len, uint32_t loop_start, uint32_t loop_end)
-{
-    if(!c || !data || (adpcm_type != OALGPU_ADPCM_IMA4 && adpcm_type != OALGPU_ADPCM_MS) || channels < 1 || channels > 2
-        || sample_len == 0 || loop_end > sample_len || loop_start >= (loop_end ? loop_end : 1u)
-        || samples_per_block < (adpcm_type == OALGPU_ADPCM_MS ? 3u : 2u) || samples_per_block > 65536u)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_register_adpcm: bad arguments");
-    if(c->freeBuffers.empty() && c->numBuffers >= c->desc.max_buffers) return Fail(OALGPU_ERR_CAPACITY, "buffer table full");
-    if(int rc = UseCtx(c)) return rc;
-    const uint32_t numBlocks = (sample_len + samples_per_block - 1u) / samples_per_block;
-    const size_t blockBytes = adpcm_type == OALGPU_ADPCM_MS ? size_t{(samples_per_block - 2u) / 2u + 7u} * channels
-        : size_t{(samples_per_block - 1u) / 2u + 4u} * channels;
-    const size_t nbytes = size_t{numBlocks} * blockBytes;
-    void *comp = nullptr, *pcm = nullptr;
-    HIP_TRY(hipMalloc(&comp, nbytes + 16));
-    hipError_t e = hipMemcpy(comp, data, nbytes, hipMemcpyHostToDevice);
-    if(e == hipSuccess) e = hipMalloc(&pcm, size_t{sample_len} * channels * sizeof(int16_t) + 16);
-    if(e != hipSuccess) { (void)hipFree(comp); return Fail(OALGPU_ERR_HIP, hipGetErrorString(e)); }
-    LaunchDecodeAdpcm(c->stream, adpcm_type == OALGPU_ADPCM_MS, static_cast<const uint8_t*>(comp), static_cast<int16_t*>(pcm),
-        numBlocks, samples_per_block, channels, sample_len);
-    e = hipGetLastError();
-    if(e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(comp);
-    if(e != hipSuccess) { (void)hipFree(pcm); return Fail(OALGPU_ERR_HIP, hipGetErrorString(e)); }
-    uint32_t h = 0;
-    if(int rc = AllocBufferHandle(c, &h)) { (void)hipFree(pcm); return rc; }
-    c->bufferData[h] = pcm;
-    c->bufferLoopLen[h] = loop_end > loop_start ? loop_end - loop_start : 0u;
-    BufferItem item{pcm, OALGPU_FMT_SHORT, channels, sample_len, loop_start, loop_end, 0};
-    HIP_TRY(hipMemcpy(c->buffers.p + h, &item, sizeof(item), hipMemcpyHostToDevice));
-    return int(h);
 }
 
 /* Voice::mStartTime (core/voice.h:209): the voice starts `samples` output samples from the beginning of
@@ -230,12 +87,11 @@ int oalgpu_buffer_register_adpcm(oalgpu_context *c, const void *data, int adpcm_
  * deviceTime) * rate)); updates that end before that leave the voice untouched. */
 int oalgpu_voice_set_start_delay(oalgpu_context *c, uint32_t voice, uint32_t samples)
 {
-    if(!c || voice >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_start_delay: bad voice");
+    if(!VoiceOk(c, voice)) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_start_delay: bad voice");
     if(c->cbOfVoice[voice] >= 0) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_start_delay: not for callback voices");
     if(samples >= c->desc.sample_rate)
         return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_start_delay: a start a second or more ahead is not scheduled yet (voice.cpp:1036-1038)");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     LaunchSetStartDelay(c->stream, c->L, voice, samples);
     HIP_TRY(hipGetLastError());
     return OALGPU_OK;
@@ -243,10 +99,7 @@ int oalgpu_voice_set_start_delay(oalgpu_context *c, uint32_t voice, uint32_t sam
 
 int oalgpu_voice_set_ambi_scale(oalgpu_context *c, uint32_t voice, float xover_norm, float hf_scale, float lf_scale)
 {
-    if(!c || voice >= c->L.numVoices || !(xover_norm > 0.0f) || !(xover_norm < 0.5f))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_ambi_scale: bad arguments");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c, VoiceOk(c, voice) && xover_norm > 0.0f && xover_norm < 0.5f, "oalgpu_voice_set_ambi_scale")) return rc;
     AmbiScaleState st{};
     st.coeff = SplitterCoeff(xover_norm);
     st.hfScale = hf_scale; st.lfScale = lf_scale;
@@ -292,10 +145,9 @@ int oalgpu_context_set_nfc(oalgpu_context *c, float w1, const uint32_t channels_
 
 int oalgpu_voice_set_nfc(oalgpu_context *c, uint32_t voice, float w0)
 {
-    if(!c || voice >= c->L.numVoices || !(w0 >= 0.0f)) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_nfc: bad arguments");
+    if(!VoiceOk(c, voice) || !(w0 >= 0.0f)) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_nfc: bad arguments");
     if(!c->L.nfc) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_nfc: oalgpu_context_set_nfc first");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     NfcDesign d = c->nfcDevice;                  // chandata.NFCtrlFilter = device->mNFCtrlFilter, then adjust(w0)
     NfcAdjust(w0, d);
     NfcState st{};
@@ -304,27 +156,6 @@ int oalgpu_voice_set_nfc(oalgpu_context *c, uint32_t voice, float w0)
     LaunchSetNfc(c->stream, c->L, voice, st);
     HIP_TRY(hipGetLastError());
     return OALGPU_OK;
-}
-
-int oalgpu_buffer_channel_view(oalgpu_context *c, int buffer, uint32_t channel)
-{
-    if(!c || !BufferLive(c, buffer) || c->bufHost[size_t(buffer)].released) return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_channel_view: bad buffer");
-    if(c->freeBuffers.empty() && c->numBuffers >= c->desc.max_buffers) return Fail(OALGPU_ERR_CAPACITY, "buffer table full");
-    if(int rc = UseCtx(c)) return rc;
-    static const size_t bytesPer[7] = {1, 2, 4, 4, 8, 1, 1};
-    BufferItem item{};
-    HIP_TRY(hipMemcpy(&item, c->buffers.p + buffer, sizeof(item), hipMemcpyDeviceToHost));
-    if(channel >= item.frameStep) return Fail(OALGPU_ERR_INVALID, "oalgpu_buffer_channel_view: channel >= frame_step");
-    item.data = static_cast<const char*>(item.data) + size_t{channel} * bytesPer[item.fmt];
-    uint32_t h = 0;
-    if(int rc = AllocBufferHandle(c, &h)) return rc;
-    item.next = 0;
-    HIP_TRY(hipMemcpy(c->buffers.p + h, &item, sizeof(item), hipMemcpyHostToDevice));
-    c->bufferData[h] = nullptr;                            // the storage belongs to `buffer`: the view holds it
-    c->bufferLoopLen[h] = c->bufferLoopLen[size_t(buffer)];
-    c->bufHost[h].parent = buffer;
-    ++c->bufHost[size_t(buffer)].refs;
-    return int(h);
 }
 
 static int BuildParamRecords(oalgpu_context *c, const uint32_t *voices, const oalgpu_voice_params *params,
@@ -384,15 +215,13 @@ int oalgpu_voice_set_params(oalgpu_context *c, const uint32_t *voices, const oal
     if(!c || !voices || !params) return Fail(OALGPU_ERR_INVALID, "null argument");
     if(count == 0) return OALGPU_OK;
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     if(int rc = BuildParamRecords(c, voices, params, count, c->paramHost)) return rc;
     NoteCallbackSteps(c, voices, params, count);
-    if(c->paramDev.n < count) HIP_TRY(c->paramDev.alloc(count));
-    HIP_TRY(hipMemcpyAsync(c->paramDev.p, c->paramHost.data(), count * sizeof(ParamRecord), hipMemcpyHostToDevice, c->stream));
+    if(int rc = StageRecords(c->stream, c->paramDev, c->paramHost.data(), count)) return rc;
     LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(count));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));   // paramHost is reused by the next call
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return OALGPU_OK;
 }
 
@@ -405,8 +234,7 @@ int oalgpu_voice_set_hrtf_targets(oalgpu_context *c, const uint32_t *voices, con
     if(count == 0) return OALGPU_OK;
     if(!c->L.hrtf) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_hrtf_targets: HRTF contexts only");
     if(!c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     std::vector<TargetRecord> recs(count);
     for(size_t i = 0; i < count; ++i)
     {
@@ -414,16 +242,13 @@ int oalgpu_voice_set_hrtf_targets(oalgpu_context *c, const uint32_t *voices, con
             return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_hrtf_targets: bad voice index or delay (MaxHrirDelay = 63)");
         recs[i] = TargetRecord{voices[i], {delays[2 * i], delays[2 * i + 1]}, gains[i]};
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));           // (the staging buffers of the previous call may still be read)
-    if(c->tgtRecs.n < count) { HIP_TRY(c->tgtRecs.alloc(count)); HIP_TRY(c->tgtCoeffs.alloc(count * kHrirLen * 2)); }
-    HIP_TRY(hipMemcpyAsync(c->tgtRecs.p, recs.data(), count * sizeof(TargetRecord), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->tgtCoeffs.p, coeffs, count * kHrirLen * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if(int rc = StageRecords(c->stream, c->tgtRecs, recs.data(), count)) return rc;
+    if(int rc = StageRecords(c->stream, c->tgtCoeffs, coeffs, count * kHrirLen * 2)) return rc;
     LaunchApplyTargets(c->stream, c->L, c->tgtRecs.p, c->tgtCoeffs.p, uint32_t(count));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the caller's arrays and `recs` are free again
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return OALGPU_OK;
 }
-
 
 int oalgpu_param_block_create(oalgpu_context *c, const uint32_t *voices, const oalgpu_voice_params *params,
     size_t count, oalgpu_param_block **out)
@@ -487,8 +312,7 @@ int oalgpu_param_block_apply(oalgpu_context *c, oalgpu_param_block *b)
     }
     else
     {
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     LaunchApplyParams(c->stream, c->L, b->recs.p, b->count);
     HIP_TRY(hipGetLastError());
     }
@@ -560,8 +384,7 @@ int oalgpu_voice_move_async(oalgpu_context *c, const oalgpu_voice_move *pans, si
     if(!c->L.hrtf) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_move_async: HRTF contexts only");
     if(!c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
     if(count > c->L.numVoices) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_move_async: more records than voices");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     if(c->panCap < count)
     {   // (grows only while nothing is in flight: the first call, or a larger batch than ever before)
         if(int rc = oalgpu_sync(c)) return rc;
@@ -598,7 +421,6 @@ int oalgpu_voice_move_async(oalgpu_context *c, const oalgpu_voice_move *pans, si
     return OALGPU_OK;
 }
 
-
 /* ---- panning on the GPU: CalcDirectionCoeffs + ComputePanGains (core/mixer.h:68-73, core/mixer.cpp:16-102) ---- */
 static int UploadAmbiMap(DevBuf<AmbiMapEntry> &dst, size_t at, const uint8_t *index, const float *scale, uint32_t n)
 {
@@ -631,8 +453,7 @@ int oalgpu_slot_set_ambi_map(oalgpu_context *c, uint32_t slot, const uint8_t *in
 int oalgpu_voice_set_pan(oalgpu_context *c, const uint32_t *voices, const oalgpu_voice_pan *pans, size_t count)
 {
     if(!c || !voices || !pans || count == 0) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_pan: bad arguments");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
     std::vector<PanRecord> recs(count);
     for(size_t i = 0; i < count; ++i)
     {
@@ -643,28 +464,20 @@ int oalgpu_voice_set_pan(oalgpu_context *c, const uint32_t *voices, const oalgpu
         r.spread = pans[i].spread; r.dryGain = pans[i].dry_gain;
         std::memcpy(r.sendGain, pans[i].send_gain, sizeof(r.sendGain));
     }
-    // (the records of the previous call may still be read by its kernel)
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if(c->panRecs.n < count) HIP_TRY(c->panRecs.alloc(count));
-    HIP_TRY(hipMemcpyAsync(c->panRecs.p, recs.data(), count * sizeof(PanRecord), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if(int rc = StageRecords(c->stream, c->panRecs, recs.data(), count)) return rc;
     LaunchPanGains(c->stream, c->L, c->panRecs.p, uint32_t(count), c->dryMap.p, c->wetMaps.p);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return OALGPU_OK;
 }
 
 int oalgpu_voice_set_state(oalgpu_context *c, uint32_t voice, int play_state)
 {
-    if(!c || voice >= c->L.numVoices || play_state < OALGPU_VOICE_STOPPED || play_state > OALGPU_VOICE_PENDING)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_state: bad arguments");
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = FlushInits(c)) return rc;
+    if(int rc = BeginVoiceCall(c, VoiceOk(c, voice) && play_state >= OALGPU_VOICE_STOPPED && play_state <= OALGPU_VOICE_PENDING, "oalgpu_voice_set_state")) return rc;
     const int32_t st = play_state;
     HIP_TRY(hipMemcpyAsync(&c->ctl.p[voice].playState, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if(c->cbOfVoice[voice] >= 0) c->cbVoices[size_t(c->cbOfVoice[voice])].state = play_state;
-    if(play_state == OALGPU_VOICE_STOPPED) SetVoiceHead(c, voice, -1);      // (a released buffer the slot was the last to hold is freed: hipFree waits for the device)
+    if(play_state == OALGPU_VOICE_STOPPED) FreeStorage(c->buf.stop(voice));     // (a released buffer the slot was the last to hold is freed)
     return OALGPU_OK;
 }
-
-
