@@ -2,7 +2,9 @@
 // HBM allocation/upload, parameter preparation that the reference does with libm on its mixer
 // thread (resampler state, biquad design), and kernel launches on the context's stream.
 // No CPU fallback exists anywhere in this file: without a HIP device every entry point fails.
-// (The rest of the C-ABI: api_comm.hip, api_percall.hip, api_hrtf.hip, api_buffers.hip, api_voices.hip, api_output.hip, api_poststage.hip, api_callback.hip; shared: api_context.hpp.)
+// This file: context life, the voice kernel's grid rules, the update and its entry points.
+// (The rest of the C-ABI: api_resident.hip, api_attach.hip, api_slots.hip, api_comm.hip, api_percall.hip, api_hrtf.hip,
+// api_buffers.hip, api_voices.hip, api_output.hip, api_poststage.hip, api_callback.hip; shared: api_context.hpp.)
 #include "api_context.hpp"
 namespace oalgpu {
 
@@ -13,9 +15,6 @@ int Fail(int code, const std::string &msg)
     gLastError = msg;
     return code;
 }
-
-// resident voice kernels (OALGPU_CTX_RESIDENT) running on `device` are told to leave: see ResidentState below
-void ParkResidentContexts(int device);
 
 // Every entry point that may allocate, copy synchronously or wait for the device comes through here.  A resident voice kernel
 // ends only when its host says so, and anything that synchronises the device (hipFree, a blocking hipMemcpy, the null stream)
@@ -34,8 +33,6 @@ int UseDevice(int device)
 
 } // namespace oalgpu
 
-
-
 // every entry point that enqueues work on a context or reads its state goes through here: the device (which parks a resident
 // voice kernel: whatever follows on the main stream then runs behind its end), a parameter block that was waiting for a
 // resident update, and the deferred update
@@ -52,40 +49,6 @@ int UseCtxResident(oalgpu_context *c)
     HIP_TRY(hipSetDevice(c->desc.device));
     return OALGPU_OK;
 }
-
-// ---- resident voice kernels: who is running, and how they are told to leave ----
-namespace {
-std::mutex gResLock;                        // submit / park of every context's resident state
-std::vector<oalgpu_context*> gResRunning;
-std::atomic<int> gResCount{0};
-
-// (gResLock held) the running launch finishes the updates that have been rung and ends; nothing waits here
-void ResidentParkLocked(oalgpu_context *c)
-{
-    auto &R = c->res;
-    if(!R.running) return;
-    __atomic_store_n(&R.door->exitSeq[R.launches & 3u], R.next, __ATOMIC_RELEASE);     // (R.launches: the running launch's id)
-    __builtin_ia32_sfence();                // (write-combined stores through the BAR leave the core)
-    R.running = false;
-    ++R.parks;
-    R.shortRuns = (R.next - R.launchBase < R.shortRun) ? R.shortRuns + 1u : 0u;
-    if(R.shortRuns >= 3u) { R.shortRuns = 0u; R.cooldown = 192u; }
-    const uint32_t e = (R.launches - 1u) % oalgpu_context::ResidentState::kEv;
-    R.evLast[e] = R.next;
-    gResRunning.erase(std::remove(gResRunning.begin(), gResRunning.end(), c), gResRunning.end());
-    gResCount.store(int(gResRunning.size()), std::memory_order_relaxed);
-}
-} // namespace
-
-namespace oalgpu {
-void ParkResidentContexts(int device)
-{
-    if(gResCount.load(std::memory_order_relaxed) == 0) return;
-    std::lock_guard<std::mutex> g(gResLock);
-    std::vector<oalgpu_context*> run = gResRunning;
-    for(oalgpu_context *c : run) if(c->desc.device == device) ResidentParkLocked(c);
-}
-} // namespace oalgpu
 
 // (shared with the other C-ABI translation units: api_context.hpp)
 
@@ -122,8 +85,6 @@ int FlushInits(oalgpu_context *c)
     return OALGPU_OK;
 }
 
-static void SetRowsGroups(oalgpu_context *c);      // (voice_rows.hip's grid; defined beside RebalanceWaveGroups)
-
 // the device's compute units (256 on an MI355X, the figure assumed when the query fails)
 uint32_t DeviceComputeUnits(int device)
 {
@@ -131,6 +92,65 @@ uint32_t DeviceComputeUnits(int device)
     if(hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) return uint32_t(prop.multiProcessorCount);
     (void)hipGetLastError();
     return 256u;
+}
+
+// An EAX reverb instance is ONE workgroup that needs a compute unit's LDS nearly to itself (128 KB: both pipelines' rows,
+// csrc/reverb_kernels.hip), and it runs on the post stream beside the NEXT update's voice kernel.  A voice kernel whose grid fills
+// the machine exactly (two 78 KB workgroups on every CU) then finds the instances' CUs taken: the workgroups it cannot place wait
+// for a second round, and the launch lasts 1.6 times as long (BASELINE configs[3]: 110 -> 174 us in every other update, the
+// reverbs 85 -> 170 us in the updates between, profiles/r5/evidence/step_timeline_config4.txt).  With reverbs attached the
+// automatic voices-per-workgroup choice therefore leaves the instances their CUs: a few more voices per wavefront, so that the
+// grid fits on the CUs that are left -- one round, and the reverbs run beside it undisturbed.
+// voice_rows.hip's grid: one workgroup of eight wavefronts per compute unit -- the compute units the attached EAX reverb instances need
+// (a whole CU's LDS each, beside the NEXT update's voice kernel, see above) left out --, the voices dealt evenly
+static void SetRowsGroups(oalgpu_context *c)
+{
+    DeviceLayout &L = c->L;
+    const uint32_t reverbs = AttachedReverbs(c);
+    const uint32_t cus = DeviceComputeUnits(c->desc.device);
+    const uint32_t waves = RowsWavesPerGroup();
+    uint32_t groups = std::min<uint32_t>(cus > reverbs ? cus - reverbs : 1u, (L.numVoices + waves - 1u) / waves);
+    if(c->desc.voices_per_group) groups = (L.numVoices + c->desc.voices_per_group - 1u) / c->desc.voices_per_group;
+    groups = std::max<uint32_t>(1u, std::min<uint32_t>(groups, c->groupsAllocated));
+    L.rowsVpg = (L.numVoices + groups - 1u) / groups;
+    L.numGroups = (L.numVoices + L.rowsVpg - 1u) / L.rowsVpg;
+    L.numLineGroups = L.numGroups;
+}
+
+int RebalanceWaveGroups(oalgpu_context *c)
+{
+    if(c->useWave && c->L.rows8)
+    {
+        const uint32_t before = c->L.rowsVpg;
+        DeviceLayout T = c->L;
+        SetRowsGroups(c);
+        if(c->L.rowsVpg != before)
+        {   // (the streams may still run launches of the old grid)
+            const DeviceLayout N = c->L;
+            c->L = T;
+            if(int rc = oalgpu_sync(c)) return rc;
+            c->L = N;
+        }
+        return OALGPU_OK;
+    }
+    if(!c->useWave || c->desc.voices_per_group != 0u || c->L.wave16) return OALGPU_OK;
+    const uint32_t reverbs = AttachedReverbs(c);
+    hipDeviceProp_t prop{};
+    if(hipGetDeviceProperties(&prop, c->desc.device) != hipSuccess || prop.multiProcessorCount <= 0) { (void)hipGetLastError(); return OALGPU_OK; }
+    const uint32_t cus = uint32_t(prop.multiProcessorCount);
+    const uint32_t slots = 2u * (cus > reverbs ? cus - reverbs : 1u);          // two voice workgroups per compute unit
+    DeviceLayout &L = c->L;
+    uint32_t vpw = std::max<uint32_t>(1u, (c->desc.max_voices + 2047u) / 2048u);  // (oalgpu_context_create's rule)
+    const uint32_t full = 2u * cus;
+    auto groupsOf = [&](uint32_t w) { DeviceLayout T = L; T.waveVoices = w; return WaveKernelGroups(T); };
+    // only a grid that was meant to fill the machine in one round is thinned out (smaller scenes leave room anyway)
+    if(reverbs && groupsOf(vpw) <= full) { while(groupsOf(vpw) > slots) ++vpw; }
+    if(vpw == L.waveVoices) return OALGPU_OK;
+    if(int rc = oalgpu_sync(c)) return rc;
+    L.waveVoices = vpw;
+    L.numGroups = std::max<uint32_t>(1u, WaveKernelGroups(L));       // (never more than the context's buffers were sized for)
+    L.numLineGroups = L.numGroups;
+    return OALGPU_OK;
 }
 
 int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
@@ -171,11 +191,7 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     L.hrtf = desc->hrtf ? 1u : 0u;
     L.irSize = 0; L.irStride = 8;
     L.mixLines = mixLines;
-    c->slotConv.assign(desc->num_slots, nullptr);
-    c->slotReverb.assign(desc->num_slots, nullptr);
-    c->slotEffect.assign(desc->num_slots, nullptr);
-    c->slotTarget.assign(desc->num_slots, -1);
-    c->slotDepth.assign(desc->num_slots, 0u);
+    c->slots.assign(desc->num_slots, EffectSlot{});
     c->slotOrder.resize(desc->num_slots);
     for(uint32_t i = 0; i < desc->num_slots; ++i) c->slotOrder[i] = i;
     HIP_TRY(c->reverbTicket.alloc(1)); HIP_TRY(c->reverbTicket.zero());
@@ -293,8 +309,6 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     return OALGPU_OK;
 }
 
-static void DetachForDestroy(oalgpu_context *ctx);
-
 void oalgpu_context_destroy(oalgpu_context *ctx)
 {
     if(!ctx) return;
@@ -326,69 +340,9 @@ int AllocStreamRows(oalgpu_context *c)
     return OALGPU_OK;
 }
 
-static float *SlotWetBus(const DeviceLayout &L, uint32_t slot) { return L.bus + BusWetOffset(L) + size_t{slot} * L.wetChannels * kLine; }
-// EffectTarget of a slot (alc/alu.cpp:627-632): its target slot's wet bus, or the device's lines (dry, then real)
-static float *SlotDestination(const oalgpu_context *c, uint32_t slot)
-{
-    const int32_t target = c->slotTarget[slot];
-    return target >= 0 ? SlotWetBus(c->L, uint32_t(target)) : c->L.bus;
-}
-// EffectState::process of every slot that has an effect attached (alc/alu.cpp:2209-2257): from the slot's wet bus into its
-// destination, on stream `s`, after the buses are final.  The slots go by descending depth (c->slotOrder, host/slot_order.cpp:
-// a slot in front of the slot it targets, alu.cpp:2220-2249), so a wet bus has everything its feeders add before the slot's own
-// effects read it; everything is launched on `s`, whose order is the order of the sums.  Without targets there is one depth
-// and the order is the slot index.
-static int RunEffects(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
-{
-    const DeviceLayout &L = c->L;
-    for(uint32_t first = 0; first < L.numSlots; )
-    {
-        const uint32_t depth = c->slotDepth[c->slotOrder[first]];
-        uint32_t last = first;
-        while(last < L.numSlots && c->slotDepth[c->slotOrder[last]] == depth) ++last;
-        for(uint32_t i = first; i < last; ++i)
-        {
-            const uint32_t slot = c->slotOrder[i];
-            const float *wet = SlotWetBus(L, slot);
-            if(oalgpu_convolution *conv = c->slotConv[slot])
-            {
-                if(int rc = oalgpu_convolution_process_device(conv, s, wet, SlotDestination(c, slot), samples_to_do)) return rc;
-            }
-            if(oalgpu_effect *fx = c->slotEffect[slot])
-            {
-                if(int rc = oalgpu_effect_process_device(fx, s, wet, SlotDestination(c, slot), samples_to_do)) return rc;
-            }
-        }
-        // the EAX reverbs of the depth's slots: one launch, instances side by side, mix-out in slot order
-        oalgpu_reverb *revs[kRvBatchMax];
-        const float *wets[kRvBatchMax];
-        float *outs[kRvBatchMax];
-        uint32_t count = 0;
-        auto flush = [&]() -> int
-        {
-            if(!count) return OALGPU_OK;
-            const int rc = oalgpu_reverb_process_batch_device(revs, wets, count, outs, samples_to_do, s, c->reverbTicket.p);
-            count = 0;
-            return rc;
-        };
-        for(uint32_t i = first; i < last; ++i)
-        {
-            const uint32_t slot = c->slotOrder[i];
-            if(!c->slotReverb[slot]) continue;
-            revs[count] = c->slotReverb[slot];
-            wets[count] = SlotWetBus(L, slot);
-            outs[count] = SlotDestination(c, slot);
-            if(++count == kRvBatchMax) { if(int rc = flush()) return rc; }
-        }
-        if(int rc = flush()) return rc;
-        first = last;
-    }
-    return OALGPU_OK;
-}
-
 // Where the reduction finds the carried HrtfAccumData: in the bus block's accumulator region (in place: the serial post-process
 // and contexts that leave the post-process to their caller work there) or where the fused post-process filed it.
-static const float *CarrySource(oalgpu_context *c, bool carry)
+const float *CarrySource(oalgpu_context *c, bool carry)
 {
     const float *src = nullptr;
     if(carry && c->L.hrtf) src = c->carryInBuf ? c->carryBuf.p : c->L.bus + BusAccumOffset(c->L);
@@ -426,7 +380,7 @@ static void SplitterRunPowers(float coeff, uint32_t seg, float out[4])
 // The counters the kernels wait for only ever grow and the host keeps what they will read (postEpoch, reducedEpoch, outSeq, the
 // resident targets): those mirrors move only once the launch has been accepted -- a failed launch must not leave every later
 // one waiting for a count that never comes.
-static int PostDirectHrtfFused(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do, hipEvent_t evDone, bool resident = false)
+int PostDirectHrtfFused(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do, hipEvent_t evDone, bool resident)
 {
     const DeviceLayout &L = c->L;
     float *left = L.bus + size_t{L.numDry} * kLine;
@@ -437,14 +391,14 @@ static int PostDirectHrtfFused(oalgpu_context *c, hipStream_t s, uint32_t sample
     const uint32_t slot = c->outNext % oalgpu_context::kIoSlots;
     const bool ring = c->outRing && c->outFlags;
     const uint32_t outTarget = c->outArrivedTotal + PostResidentFirGroups();
+    const PostHrtfCall call{left, left + kLine, L.bus, L.numDry, L.bus + BusAccumOffset(L), c->carryBuf.p, spIn, spOut, c->dHfScale.p, c->dCoeffs.p,
+        c->dIrSize, samples_to_do, c->dTemp.p, c->postArrived.p, postEpoch, c->runPower, evDone, ring ? c->outHost[slot] : nullptr,
+        ring ? c->outFlags + size_t{slot} * 16 : nullptr, c->outSeq + 1u};
     auto &R = c->res;
     if(resident)
     {
         c->reduceHeld = false;
-        LaunchPostResident(s, left, left + kLine, L.bus, L.numDry, L.bus + BusAccumOffset(L), c->carryBuf.p, spIn, spOut, c->dHfScale.p, c->dCoeffs.p,
-            c->dIrSize, samples_to_do, c->dTemp.p, c->postArrived.p, postEpoch, c->runPower, evDone, ring ? c->outHost[slot] : nullptr,
-            ring ? c->outFlags + size_t{slot} * 16 : nullptr, c->outSeq + 1u, R.counters.p, R.hostFlags, (R.posts + 1u) * R.redGroups,
-            (R.posts + 1u) * R.firGroups, R.posts + 1u);
+        LaunchPostResident(s, call, R.counters.p, R.hostFlags, (R.posts + 1u) * R.redGroups, (R.posts + 1u) * R.firGroups, R.posts + 1u);
         HIP_TRY(hipGetLastError());
         ++R.posts;
     }
@@ -453,19 +407,14 @@ static int PostDirectHrtfFused(oalgpu_context *c, hipStream_t s, uint32_t sample
         c->reduceHeld = false;
         if(!c->reducedCount.p) { HIP_TRY(c->reducedCount.alloc(1)); HIP_TRY(c->reducedCount.zero()); }
         const uint32_t reducedEpoch = c->reducedEpoch + ReducePostReduceGroups(c->heldL);
-        LaunchReducePostFused(s, c->heldL, CarrySource(c, c->carryAccum && L.hrtf), left, left + kLine, L.bus, L.numDry, L.bus + BusAccumOffset(L),
-            c->carryBuf.p, spIn, spOut, c->dHfScale.p, c->dCoeffs.p, c->dIrSize, samples_to_do, c->dTemp.p, c->postArrived.p, postEpoch,
-            c->runPower, evDone, ring ? c->outHost[slot] : nullptr, ring ? c->outFlags + size_t{slot} * 16 : nullptr, c->outSeq + 1u,
-            c->outArrived.p, outTarget, c->reducedCount.p, reducedEpoch);
+        LaunchReducePostFused(s, call, c->heldL, CarrySource(c, c->carryAccum && L.hrtf), c->outArrived.p, outTarget, c->reducedCount.p, reducedEpoch);
         HIP_TRY(hipGetLastError());
         c->reducedEpoch = reducedEpoch;
         if(ring) c->outArrivedTotal = outTarget;
     }
     else
     {
-        LaunchPostDirectHrtfFused(s, left, left + kLine, L.bus, L.numDry, L.bus + BusAccumOffset(L), c->carryBuf.p, spIn, spOut,
-            c->dHfScale.p, c->dCoeffs.p, c->dIrSize, samples_to_do, c->dTemp.p, c->postArrived.p, postEpoch, c->runPower, evDone,
-            ring ? c->outHost[slot] : nullptr, ring ? c->outFlags + size_t{slot} * 16 : nullptr, c->outSeq + 1u, c->outArrived.p, outTarget);
+        LaunchPostDirectHrtfFused(s, call, c->outArrived.p, outTarget);
         HIP_TRY(hipGetLastError());
         if(ring) c->outArrivedTotal = outTarget;
     }
@@ -486,303 +435,59 @@ int JoinPost(oalgpu_context *c)
     return OALGPU_OK;
 }
 
-
-// ---- the resident voice kernel: host side (device side and protocol: kernels.hpp ResidentDoor, voice_wave.hip, post_wave.hip) ----
-bool ResidentWanted(const oalgpu_context *c, int post_process)
+// ---- the update's entry points ----
+static int RefuseWithoutHrtfData(const oalgpu_context *c)
 {
-    const auto &R = c->res;
-    return R.enabled && !R.failed && WaveKernelHasResident(c->L) && post_process && c->hrtfLoaded && c->directSet && !c->timing && c->cbVoices.empty()
-        && c->initPending.empty() && c->carryAccum && !c->comm && !c->pendingMix.active && c->useWave && c->ownStream && !c->serialOnly
-        && c->L.numReal >= 2 && c->L.numSlots == 0 && c->attached.empty();
-}
-
-// a parameter block that was waiting for a resident update is applied the launched way (the caller has parked the kernel)
-int FlushResidentBlock(oalgpu_context *c)
-{
-    oalgpu_param_block *b = c->res.pendingBlock;
-    if(!b) return OALGPU_OK;
-    c->res.pendingBlock = nullptr;
-    b->heldBy = nullptr;
-    if(int rc = FlushInits(c)) return rc;
-    LaunchApplyParams(c->stream, c->L, b->recs.p, b->count);
-    HIP_TRY(hipGetLastError());
+    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
     return OALGPU_OK;
 }
 
-static int ResidentGiveUp(oalgpu_context *c, const std::string &why)
+// What every update entry point starts with, like BeginSetter for the setters.  The refusals, in this order: a null context or a
+// sample count outside a line; (kNeedsFast) a context that does not pipeline two streams of its own; an attached context, which
+// its device context updates; (kNeedsHrtfData) an HRTF context without a data set.
+enum : uint32_t { kNeedsFast = 1u, kNeedsHrtfData = 2u };
+static int BeginUpdate(oalgpu_context *c, const char *who, uint32_t samples_to_do, uint32_t needs = 0u)
 {
-    c->res.failed = true;
-    return Fail(OALGPU_ERR_HIP, "resident voice kernel: " + why + " (the context launches per update from now on)");
+    if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
+    if((needs & kNeedsFast) && !(c->useWave && c->ownStream))
+        return Fail(OALGPU_ERR_INVALID, std::string(who) + ": needs a FAST context (wavefront kernel) on its own streams");
+    if(int rc = RefuseAttached(c, who)) return rc;
+    return (needs & kNeedsHrtfData) ? RefuseWithoutHrtfData(c) : OALGPU_OK;
 }
 
-// streams, the door, counters, partial sets: once per context, with nothing resident on the device
-static int ResidentInit(oalgpu_context *c)
+// in front of a context's voice kernel: its callback sources are asked, its attached contexts' voices go first
+static int BeforeVoices(oalgpu_context *c, uint32_t samples_to_do)
 {
-    auto &R = c->res;
-    if(int rc = UseDevice(c->desc.device)) return rc;
-    hipDeviceProp_t prop{};
-    HIP_TRY(hipGetDeviceProperties(&prop, c->desc.device));
-    // every workgroup of the launch has to be on the machine at once: nothing ever leaves to make room
-    R.groupsPerCu = uint32_t(std::max(0, WaveResidentGroupsPerCu(c->L)));
-    if(uint64_t{R.groupsPerCu} * uint32_t(prop.multiProcessorCount) < c->L.numGroups)
-        return ResidentGiveUp(c, "the device does not hold all of the launch's workgroups at once");
-    // the reduce stream between the main stream's priority class (highest) and the post stream's (lowest): a class has its own
-    // hardware queues, and a queue the resident kernel sits in never moves
-    int prioLeast = 0, prioGreatest = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&prioLeast, &prioGreatest));
-    if(prioLeast - prioGreatest < 2) return ResidentGiveUp(c, "fewer than three stream priority classes");
-    HIP_TRY(hipStreamCreateWithPriority(&R.reduceStream, hipStreamDefault, (prioLeast + prioGreatest) / 2));
-    R.doorInBar = HostStoresReachDevice(c);
-    if(R.doorInBar) HIP_TRY(hipExtMallocWithFlags(reinterpret_cast<void**>(&R.door), sizeof(ResidentDoor), hipDeviceMallocFinegrained));
-    else HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&R.door), sizeof(ResidentDoor), hipHostMallocDefault));
-    std::memset(R.door, 0, sizeof(ResidentDoor));
-    for(uint32_t &e : R.door->exitSeq) e = 0x40000000u;
-    __builtin_ia32_sfence();
-    HIP_TRY(R.counters.alloc(size_t{kRcCount} * 16)); HIP_TRY(R.counters.zero());
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&R.hostFlags), size_t{kRhCount} * 16 * sizeof(uint32_t), hipHostMallocDefault));
-    std::memset(R.hostFlags, 0, size_t{kRhCount} * 16 * sizeof(uint32_t));
-    R.setFloats = size_t{c->L.numGroups} * (kLine + kHrirLen) * 2;
-    HIP_TRY(R.part.alloc(R.setFloats * kResidentSets));
-    for(uint32_t k = 0; k < oalgpu_context::ResidentState::kEv; ++k) { HIP_TRY(hipEventCreate(&R.evStart[k])); HIP_TRY(hipEventCreate(&R.evStop[k])); }
-    R.firGroups = PostResidentFirGroups();
-    R.redGroups = uint32_t((BusFloats(c->L) + 63u) / 64u);
-    R.ready = true;
-    return OALGPU_OK;
-}
-
-// the launches whose events have fired hand over their times
-static void ResidentCollectTimes(oalgpu_context *c, bool all)
-{
-    auto &R = c->res;
-    for(uint32_t k = 0; k < oalgpu_context::ResidentState::kEv; ++k)
-    {
-        if(!R.evOpen[k] || (R.running && k == (R.launches - 1u) % oalgpu_context::ResidentState::kEv)) continue;
-        if(!all && hipEventQuery(R.evStop[k]) != hipSuccess) { (void)hipGetLastError(); continue; }
-        float ms = 0.0f;
-        if(hipEventElapsedTime(&ms, R.evStart[k], R.evStop[k]) == hipSuccess)
-        {
-            R.kernelMs += double(ms); R.kernelUpdates += R.evLast[k] - R.evFirst[k]; ++R.kernelLaunches;
-        }
-        else (void)hipGetLastError();
-        R.evOpen[k] = false;
-    }
-}
-
-static int ResidentCheckError(oalgpu_context *c)
-{
-    auto &R = c->res;
-    if(!R.hostFlags) return OALGPU_OK;
-    const uint32_t e = __atomic_load_n(R.hostFlags + 16u * kRhError, __ATOMIC_ACQUIRE);
-    if(!e) return OALGPU_OK;
-    __atomic_store_n(R.hostFlags + 16u * kRhError, 0u, __ATOMIC_RELEASE);
-    static const char *what[4] = {"", "the voice kernel waited 2 s for the host or for its reduction", "a reduction waited 2 s for the voice kernel",
-        "a reduction waited 2 s for the post-process"};
-    // where everything stood: the counters the kernels wait for, beside what the host expects them to reach
-    std::string state;
-    {
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(R.reduceStream); (void)hipStreamSynchronize(c->postStream);
-        uint32_t w[kRcCount * 16] = {};
-        uint32_t pa = 0;
-        if(hipMemcpy(w, R.counters.p, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess
-            && hipMemcpy(&pa, c->postArrived.p, sizeof(pa), hipMemcpyDeviceToHost) == hipSuccess)
-        {
-            char buf[512];
-            std::snprintf(buf, sizeof(buf), " [updates %u, launches %u, groups %u; arrive %u %u %u %u (uses %u %u %u %u), redRead %u redDone %u (per update %u), "
-                "postDone %u (posts %u x %u), postArrived %u (epoch %u), started %u (expected %u), progress %u]", R.next, R.launches, c->L.numGroups,
-                w[0], w[16], w[32], w[48], R.setUses[0], R.setUses[1], R.setUses[2], R.setUses[3], w[16 * kRcRedRead], w[16 * kRcRedDone], R.redGroups,
-                w[16 * kRcPostDone], R.posts, R.firGroups, pa, c->postEpoch, w[16 * kRcStarted], R.startedTotal,
-                __atomic_load_n(R.hostFlags + 16u * kRhProgress, __ATOMIC_ACQUIRE));
-            state = buf;
-            const uint32_t *fi = R.hostFlags + 16u * kRhFault;
-            std::snprintf(buf, sizeof(buf), " [the voice workgroup that gave up: update %u, doorbell %u, exit word %u, reduction counter %u of %u, workgroup %u, launch %u, "
-                "%u ticks; host: seq %u exit %u %u %u %u]", fi[0], fi[1], fi[2], fi[3], fi[4], fi[5], fi[6], fi[7], R.door->seq, R.door->exitSeq[0], R.door->exitSeq[1],
-                R.door->exitSeq[2], R.door->exitSeq[3]);
-            if(e == 1) state += buf;
-        }
-        else (void)hipGetLastError();
-    }
-    return ResidentGiveUp(c, std::string(e < 4 ? what[e] : "a wait timed out") + state);
-}
-
-// One update of a resident context: the doorbell, its reduction (reduce stream) and its post-process (post stream).
-// Returns 1 when the update has to go the launched way after all (the caller falls through), 0 when submitted, < 0 on errors.
-static int ResidentSubmit(oalgpu_context *c, uint32_t samples_to_do)
-{
-    auto &R = c->res;
-    if(!R.ready) { if(int rc = ResidentInit(c)) return R.failed ? 1 : rc; }
-    HIP_TRY(hipSetDevice(c->desc.device));
-    using clk = std::chrono::steady_clock;
-    std::unique_lock<std::mutex> g(gResLock);
-    const DeviceLayout &L = c->L;
-    // a new launch: prepared here, started BEHIND the update's doorbell (the kernel finds its first update rung when it comes up)
-    const bool launchNow = !R.running;
-    ResidentArgs a{};
-    uint32_t evk = 0;
-    bool timed = false;
-    if(launchNow)
-    {
-        // the reduce stream joins whatever the post stream still runs (the bus block and the carried accumulator are theirs too)
-        if(c->postPending) HIP_TRY(hipStreamWaitEvent(R.reduceStream, c->lastPostEvent ? c->lastPostEvent : c->evPostDone, 0));
-        const uint32_t k = evk = R.launches % oalgpu_context::ResidentState::kEv;
-        if(R.evOpen[k]) { HIP_TRY(hipEventSynchronize(R.evStop[k])); ResidentCollectTimes(c, false); }
-        timed = R.timeLaunches;           // (events bound to the dispatch cost the launch call ~15 us of host time)
-        a.door = R.door; a.counters = R.counters.p; a.hostFlags = R.hostFlags; a.partBase = R.part.p; a.setStride = uint32_t(R.setFloats);
-        a.base = R.next; a.endSeq = R.next + R.maxUpdates; a.redPerUpdate = R.redGroups;
-        a.startedTarget = R.startedTotal + L.numGroups; a.launchId = R.launches + 1u;
-        __atomic_store_n(&R.door->exitSeq[a.launchId & 3u], R.next + 0x40000000u, __ATOMIC_RELEASE);
-        __atomic_store_n(&R.door->seq, R.next, __ATOMIC_RELEASE);
-        __builtin_ia32_sfence();
-    }
-    {   // the host stays at most kResidentDepth updates ahead of the post-process (doorbell slots, queue depth)
-        const auto deadline = clk::now() + std::chrono::seconds(5);
-        uint32_t spins = 0;
-        while(int32_t(R.posts - __atomic_load_n(R.hostFlags + 16u * kRhProgress, __ATOMIC_ACQUIRE)) >= int32_t(kResidentDepth))
-        {
-            __builtin_ia32_pause();
-            if((++spins & 0x3ffu) == 0 && clk::now() > deadline)
-            {
-                ResidentParkLocked(c);
-                g.unlock();
-                (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(R.reduceStream); (void)hipStreamSynchronize(c->postStream);
-                if(int rc = ResidentCheckError(c)) return rc;
-                return ResidentGiveUp(c, "the post-process made no progress for 5 s");
-            }
-        }
-    }
-    if(__atomic_load_n(R.hostFlags + 16u * kRhError, __ATOMIC_RELAXED))
-    {
-        ResidentParkLocked(c);
-        g.unlock();
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(R.reduceStream); (void)hipStreamSynchronize(c->postStream);
-        return ResidentCheckError(c);
-    }
+    if(!c->cbVoices.empty()) { if(int rc = ServiceCallbacks(c, samples_to_do)) return rc; }
+    if(!c->attached.empty()) { if(int rc = MixAttached(c, samples_to_do)) return rc; }
     c->outRingWritten = false;
-    // ---- the doorbell: the slot first, then the sequence number
-    oalgpu_param_block *b = R.pendingBlock;
-    R.pendingBlock = nullptr;
-    if(b) b->heldBy = nullptr;
-    ResidentSlot &sl = R.door->slot[R.next % kResidentSlots];
-    sl.recs = b ? reinterpret_cast<unsigned long long>(b->recs.p) : 0ull;
-    sl.map = b ? reinterpret_cast<unsigned long long>(b->voiceToRec.p) : 0ull;
-    sl.rows = b ? reinterpret_cast<unsigned long long>(b->rows.p) : 0ull;
-    sl.samples = samples_to_do;
-    __builtin_ia32_sfence();
-    __atomic_store_n(&R.door->seq, R.next + 1u, __ATOMIC_RELEASE);
-    __builtin_ia32_sfence();
-    if(launchNow)
-    {
-        const uint32_t k = evk;
-        HIP_TRY(LaunchVoiceWaveResident(c->stream, L, a, timed ? R.evStart[k] : nullptr, timed ? R.evStop[k] : nullptr));
-        R.evOpen[k] = timed; R.evFirst[k] = R.next; R.evLast[k] = R.next;
-        ++R.launches; R.startedTotal = a.startedTarget; R.endSeq = a.endSeq; R.launchBase = R.next;
-        // Nothing that waits for this kernel may get onto the machine in front of it: a reduction that polls for workgroups which
-        // find no room beside it would wait for ever.  The last workgroup to start says so (a pinned word): the doorbell is rung at
-        // once -- the workgroups that are there start on the update -- and the host looks for the word only in front of the first
-        // reduction it launches (awaitStarted), which nobody needs before the voices of the update are through.
-        R.awaitStarted = a.launchId;
-        R.running = true;
-        gResRunning.push_back(c);
-        gResCount.store(int(gResRunning.size()), std::memory_order_relaxed);
-    }
-    // ---- the update's reduction and post-process: launches of their own that wait for device counters
-    const uint32_t set = R.next % kResidentSets;
-    if(R.awaitStarted)
-    {
-        const uint32_t id = R.awaitStarted;
-        R.awaitStarted = 0u;
-        const auto deadline = clk::now() + std::chrono::seconds(5);
-        uint32_t spins = 0;
-        while(__atomic_load_n(R.hostFlags + 16u * kRhResident, __ATOMIC_ACQUIRE) != id)
-        {
-            __builtin_ia32_pause();
-            if((++spins & 0x3ffu) == 0 && clk::now() > deadline)
-            {   // (it may still start, and the update has been rung: it is told to leave behind that update; the update is lost)
-                ++R.next;
-                ResidentParkLocked(c);
-                g.unlock();
-                (void)hipStreamSynchronize(c->stream);
-                return ResidentGiveUp(c, "its workgroups did not all start within 5 s");
-            }
-        }
-    }
-    if(R.copyPending) { HIP_TRY(hipStreamWaitEvent(R.reduceStream, R.copyPending, 0)); R.copyPending = nullptr; }
-    DeviceLayout Lr = L;
-    Lr.partHrtf = R.part.p + size_t{set} * R.setFloats;
-    LaunchBusReduceResident(R.reduceStream, Lr, CarrySource(c, true), R.counters.p, R.hostFlags, set, (R.setUses[set] + 1u) * L.numGroups,
-        R.posts * R.firGroups);
-    HIP_TRY(hipGetLastError());
-    ++R.setUses[set];
-    c->lastPostEvent = c->evPostDone;
-    if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, c->limOn ? nullptr : c->evPostDone, true)) return rc;
-    if(c->limOn)
-    {   // the limiter behind the update's post-process; the next update's reduction (reduce stream) rewrites the lines it limits
-        if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc;
-        HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));
-        R.copyPending = c->evPostDone;
-    }
-    c->postPending = true;
-    ++R.next;
-    ++c->updatesSubmitted;
-    R.evLast[(R.launches - 1u) % oalgpu_context::ResidentState::kEv] = R.next;
-    if(R.next == R.endSeq)
-    {   // the launch's own bound: it leaves by itself behind this update; the next one starts a new launch
-        R.running = false;
-        gResRunning.erase(std::remove(gResRunning.begin(), gResRunning.end(), c), gResRunning.end());
-        gResCount.store(int(gResRunning.size()), std::memory_order_relaxed);
-    }
     return OALGPU_OK;
 }
 
-static int RefuseAttached(const oalgpu_context *c, const char *who)
+// the end of a timed update (oalgpu_set_timing) on stream `s`
+static int EndTimedUpdate(oalgpu_context *c, hipStream_t s)
 {
-    if(!c->attachedTo) return OALGPU_OK;
-    return Fail(OALGPU_ERR_INVALID, std::string(who) + ": the context is attached (oalgpu_context_attach): its device context updates it");
-}
-
-static int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do);
-
-// (device context) the attached contexts' voices and reductions of this update, each on its own main stream, in front of the
-// device context's own voice kernel: the kernels run side by side
-static int MixAttached(oalgpu_context *c, uint32_t samples_to_do)
-{
-    for(oalgpu_context *a : c->attached) { if(int rc = MixVoicesSerial(a, samples_to_do)) return rc; }
-    return OALGPU_OK;
-}
-
-// (device context) behind its own reduction on stream `s`, in front of its effect slots and post stage: the attached contexts'
-// effect slots, then their lines into the device context's (BusMergeKernel) once their last launches are through
-static int MergeAttached(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do)
-{
-    for(oalgpu_context *a : c->attached)
-    {
-        if(int rc = RunEffects(a, a->stream, samples_to_do)) return rc;
-        HIP_TRY(hipEventRecord(a->evBusFinal, a->stream));
-        HIP_TRY(hipStreamWaitEvent(s, a->evBusFinal, 0));
-    }
-    LaunchBusMerge(s, c->mergeHeads.p, c->mergeRows.p, c->mergeLines, samples_to_do);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->evMerged, s));
-    c->mergeInFlight = true;
+    if(!c->timing) return OALGPU_OK;
+    HIP_TRY(hipEventRecord(c->evEnd, s));
+    c->timed = true;
     return OALGPU_OK;
 }
 
 int oalgpu_mix_voices(oalgpu_context *c, uint32_t samples_to_do)
 {
-    if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
-    if(int rc = RefuseAttached(c, "oalgpu_mix_voices")) return rc;
+    if(int rc = BeginUpdate(c, "oalgpu_mix_voices", samples_to_do)) return rc;
     return MixVoicesSerial(c, samples_to_do);
 }
 
-// oalgpu_mix_voices; also what a device context does for each of its attached contexts
-static int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do)
+// oalgpu_mix_voices; also what a device context does for each of its attached contexts (which pass no entry point: the data set
+// is asked for here)
+int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do)
 {
-    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
+    if(int rc = RefuseWithoutHrtfData(c)) return rc;
     if(int rc = UseCtx(c)) return rc;
     if(int rc = FlushInits(c)) return rc;
     if(int rc = JoinPost(c)) return rc;
-    if(!c->cbVoices.empty()) { if(int rc = ServiceCallbacks(c, samples_to_do)) return rc; }
-    if(!c->attached.empty()) { if(int rc = MixAttached(c, samples_to_do)) return rc; }
-    c->outRingWritten = false;
+    if(int rc = BeforeVoices(c, samples_to_do)) return rc;
     if(c->useWave)    // (timing: the two events are bound to the dispatch itself -- the kernel's own start and end)
         HIP_TRY(LaunchVoiceWave(c->stream, c->L, samples_to_do, c->profArg(), c->timing ? c->evStart : nullptr, c->timing ? c->evVoice : nullptr));
     else
@@ -797,14 +502,12 @@ static int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do)
     LaunchBusReduce(c->stream, c->L, samples_to_do, CarrySource(c, c->useWave && c->carryAccum));
     HIP_TRY(hipGetLastError());
     if(int rc = CommReduceBus(c, c->stream)) return rc;
-    if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
-    return OALGPU_OK;
+    return EndTimedUpdate(c, c->stream);
 }
 
 int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
 {
-    if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
-    if(int rc = RefuseAttached(c, "oalgpu_post_process")) return rc;
+    if(int rc = BeginUpdate(c, "oalgpu_post_process", samples_to_do)) return rc;
     if(int rc = UseCtx(c)) return rc;
     if(int rc = JoinPost(c)) return rc;
     if(!c->attached.empty()) { if(int rc = MergeAttached(c, c->stream, samples_to_do)) return rc; }
@@ -812,8 +515,7 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
     if(!c->L.hrtf)
     {
         if(int rc = RunSpeakerPost(c, c->stream, samples_to_do)) return rc;
-        if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
-        return OALGPU_OK;
+        return EndTimedUpdate(c, c->stream);
     }
     const DeviceLayout &L = c->L;
     if(L.numReal < 2) return Fail(OALGPU_ERR_INVALID, "HRTF post-process needs two real output lines");
@@ -830,17 +532,14 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
             c->dHfScale.p, c->dCoeffs.p, c->dIrSize, samples_to_do, c->dTemp.p);
     HIP_TRY(hipGetLastError());
     if(int rc = RunLimiter(c, c->stream, samples_to_do)) return rc;
-    if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->stream)); c->timed = true; }
-    return OALGPU_OK;
+    return EndTimedUpdate(c, c->stream);
 }
 
 static int RunMixUpdate(oalgpu_context *c, uint32_t samples_to_do, int post_process, oalgpu_param_block *next);
 
 int oalgpu_mix_update(oalgpu_context *c, uint32_t samples_to_do, int post_process)
 {
-    if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
-    if(int rc = RefuseAttached(c, "oalgpu_mix_update")) return rc;
-    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
+    if(int rc = BeginUpdate(c, "oalgpu_mix_update", samples_to_do, kNeedsHrtfData)) return rc;
     if(c->res.cooldown) --c->res.cooldown;
     else if(ResidentWanted(c, post_process))
     {   // the resident voice kernel: a doorbell, the update's reduction and its post-process
@@ -913,16 +612,10 @@ int oalgpu_mix_update_run(oalgpu_context *c, oalgpu_param_block *const *param_bl
 
 int oalgpu_mix_voices_overlapped(oalgpu_context *c, uint32_t samples_to_do)
 {
-    if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
-    if(!(c->useWave && c->ownStream))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_mix_voices_overlapped: needs a FAST context (wavefront kernel) on its own streams");
-    if(int rc = RefuseAttached(c, "oalgpu_mix_voices_overlapped")) return rc;
-    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, "HRTF context without a data set");
+    if(int rc = BeginUpdate(c, "oalgpu_mix_voices_overlapped", samples_to_do, kNeedsFast | kNeedsHrtfData)) return rc;
     if(int rc = UseCtx(c)) return rc;
     if(int rc = FlushInits(c)) return rc;
-    if(!c->cbVoices.empty()) { if(int rc = ServiceCallbacks(c, samples_to_do)) return rc; }
-    if(!c->attached.empty()) { if(int rc = MixAttached(c, samples_to_do)) return rc; }
-    c->outRingWritten = false;
+    if(int rc = BeforeVoices(c, samples_to_do)) return rc;
     const uint32_t p = c->parity;
     DeviceLayout L = c->L;
     L.partHrtf = c->partHrtfBuf[p];
@@ -965,10 +658,7 @@ void *oalgpu_post_stream(oalgpu_context *c) { return c ? static_cast<void*>(c->p
 
 int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, int post_process)
 {
-    if(!c || samples_to_do == 0 || samples_to_do > kLine) return Fail(OALGPU_ERR_INVALID, "samples_to_do must be 1..1024");
-    if(!(c->useWave && c->ownStream))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_post_process_overlapped: needs a FAST context (wavefront kernel) on its own streams");
-    if(int rc = RefuseAttached(c, "oalgpu_post_process_overlapped")) return rc;
+    if(int rc = BeginUpdate(c, "oalgpu_post_process_overlapped", samples_to_do, kNeedsFast)) return rc;
     if(post_process && c->L.hrtf && c->L.numReal < 2) return Fail(OALGPU_ERR_INVALID, "HRTF post-process needs two real output lines");
     if(int rc = UseCtx(c)) return rc;
     const DeviceLayout &L = c->L;
@@ -991,7 +681,7 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
         c->lastPostEvent = c->evPostDone;
         if(post_process) { if(int rc = RunSpeakerPost(c, c->postStream, samples_to_do)) return rc; }
     }
-    if(c->timing) { HIP_TRY(hipEventRecord(c->evEnd, c->postStream)); c->timed = true; }
+    if(int rc = EndTimedUpdate(c, c->postStream)) return rc;
     if(!postDoneBound) HIP_TRY(hipEventRecord(c->evPostDone, c->postStream));
     c->postPending = true;
     return OALGPU_OK;
@@ -1016,116 +706,6 @@ int oalgpu_sync(oalgpu_context *c)
     c->mergeInFlight = false;
     if(c->res.ready) { ResidentCollectTimes(c, true); if(int rc = ResidentCheckError(c)) return rc; }
     return OALGPU_OK;
-}
-
-// ---- several contexts on one device (ProcessContexts, alc/alu.cpp:2177-2273; include/oalgpu.h) ----
-// The merge's table of a device context, from its attached contexts' maps: per destination line the contributing lines in
-// attach order (within a context: in line order).  The caller has waited for everything that may still read the old table.
-static int RebuildMergeTable(oalgpu_context *d)
-{
-    const uint32_t lines = d->L.numDry + d->L.numReal;
-    std::vector<BusMergeHead> heads;
-    std::vector<BusMergeRow> rows;
-    std::vector<int32_t> last(lines, -1);
-    for(uint32_t line = 0; line < lines; ++line)
-        for(const oalgpu_context *a : d->attached)
-            for(size_t i = 0; i < a->attachMap.size(); ++i)
-            {
-                if(a->attachMap[i] != int32_t(line)) continue;
-                const int32_t r = int32_t(rows.size());
-                rows.push_back(BusMergeRow{a->L.bus + i * kLine, -1, 0u});
-                if(last[line] < 0) heads.push_back(BusMergeHead{d->L.bus + size_t{line} * kLine, r, 0u});
-                else rows[size_t(last[line])].next = r;
-                last[line] = r;
-            }
-    // (built beside the old table and swapped in whole: a failed allocation leaves the old one, and its contexts merged)
-    DevBuf<BusMergeHead> newHeads;
-    DevBuf<BusMergeRow> newRows;
-    if(!heads.empty())
-    {
-        HIP_TRY(newHeads.alloc(heads.size())); HIP_TRY(newHeads.upload(heads.data(), heads.size()));
-        HIP_TRY(newRows.alloc(rows.size())); HIP_TRY(newRows.upload(rows.data(), rows.size()));
-    }
-    std::swap(d->mergeHeads.p, newHeads.p); std::swap(d->mergeHeads.n, newHeads.n);
-    std::swap(d->mergeRows.p, newRows.p); std::swap(d->mergeRows.n, newRows.n);
-    d->mergeLines = uint32_t(heads.size());
-    return OALGPU_OK;
-}
-
-static void Unlink(oalgpu_context *a)
-{
-    oalgpu_context *d = a->attachedTo;
-    d->attached.erase(std::remove(d->attached.begin(), d->attached.end(), a), d->attached.end());
-    a->attachedTo = nullptr;
-    a->attachMap.clear();
-    d->mergeInFlight = false;
-}
-
-int oalgpu_context_attach(oalgpu_context *d, oalgpu_context *a, const int32_t *line_map)
-{
-    const std::string w = "oalgpu_context_attach: ";
-    if(!d || !a || !line_map) return Fail(OALGPU_ERR_INVALID, w + "null argument");
-    if(d == a) return Fail(OALGPU_ERR_INVALID, w + "a context cannot be attached to itself");
-    if(a->attachedTo) return Fail(OALGPU_ERR_INVALID, w + "the context is already attached");
-    if(d->attachedTo) return Fail(OALGPU_ERR_INVALID, w + "the device context is itself attached (no nesting)");
-    if(!a->attached.empty()) return Fail(OALGPU_ERR_INVALID, w + "the context has attached contexts of its own (no nesting)");
-    if(d->desc.device != a->desc.device) return Fail(OALGPU_ERR_INVALID, w + "the contexts are on different devices");
-    if(d->desc.sample_rate != a->desc.sample_rate) return Fail(OALGPU_ERR_INVALID, w + "the contexts have different sample rates");
-    if(a->L.hrtf) return Fail(OALGPU_ERR_INVALID, w + "an HRTF context cannot be attached (HRTF voices belong to the device context)");
-    if(a->post != PostKind::None) return Fail(OALGPU_ERR_INVALID, w + "the context has a post-process installed (the device context post-processes)");
-    if(a->limOn) return Fail(OALGPU_ERR_INVALID, w + "the context has an output limiter (the device context limits)");
-    if(a->distLines) return Fail(OALGPU_ERR_INVALID, w + "the context has distance compensation (the device context compensates)");
-    if(a->outType != OALGPU_OUT_F32 || a->ditherDepth > 0.0f)
-        return Fail(OALGPU_ERR_INVALID, w + "the context has an output conversion (oalgpu_set_output: the device context converts)");
-    if(d->comm || a->comm) return Fail(OALGPU_ERR_INVALID, w + "a context with a collective (oalgpu_comm_init) takes and is no attachment");
-    if(!a->ownStream) return Fail(OALGPU_ERR_INVALID, w + "the context is on a caller-owned stream (oalgpu_set_stream)");
-    const uint32_t srcLines = a->L.numDry + a->L.numReal, dstLines = d->L.numDry + d->L.numReal;
-    for(uint32_t i = 0; i < srcLines; ++i)
-        if(line_map[i] < -1 || line_map[i] >= int32_t(dstLines))
-            return Fail(OALGPU_ERR_INVALID, w + "map entry " + std::to_string(i) + " is out of range (-1 .. " + std::to_string(dstLines - 1u) + ")");
-    // the work in flight of both (a resident voice kernel leaves, a deferred update is submitted)
-    if(int rc = oalgpu_sync(d)) return rc;
-    if(int rc = oalgpu_sync(a)) return rc;
-    // ordering between streams of one device only: no system-scope fence (see oalgpu_context_create)
-    if(!a->evBusFinal) HIP_TRY(hipEventCreateWithFlags(&a->evBusFinal, hipEventDisableTiming | hipEventDisableSystemFence));
-    if(!d->evMerged) HIP_TRY(hipEventCreateWithFlags(&d->evMerged, hipEventDisableTiming | hipEventDisableSystemFence));
-    a->attachMap.assign(line_map, line_map + srcLines);
-    a->attachedTo = d;
-    d->attached.push_back(a);
-    if(int rc = RebuildMergeTable(d))
-    {
-        Unlink(a);
-        (void)RebuildMergeTable(d);
-        return rc;
-    }
-    return OALGPU_OK;
-}
-
-int oalgpu_context_detach(oalgpu_context *a)
-{
-    if(!a) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_detach: null argument");
-    oalgpu_context *d = a->attachedTo;
-    if(!d) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_detach: the context is not attached");
-    if(int rc = oalgpu_sync(d)) return rc;          // (waits for the attached contexts' streams as well)
-    Unlink(a);
-    return RebuildMergeTable(d);
-}
-
-// oalgpu_context_destroy of a context that has, or is, an attachment: the links go whatever the device says
-static void DetachForDestroy(oalgpu_context *ctx)
-{
-    if(oalgpu_context *d = ctx->attachedTo)
-    {
-        (void)oalgpu_sync(d);
-        Unlink(ctx);
-        (void)RebuildMergeTable(d);
-    }
-    if(!ctx->attached.empty())
-    {
-        (void)oalgpu_sync(ctx);
-        while(!ctx->attached.empty()) Unlink(ctx->attached.back());
-        ctx->mergeLines = 0;
-    }
 }
 
 int oalgpu_set_timing(oalgpu_context *c, int enable)
@@ -1179,146 +759,6 @@ int oalgpu_debug_wave_times(oalgpu_context *c, unsigned long long *out, uint32_t
 
 #endif // OALGPU_MEASUREMENT
 
-int oalgpu_slot_set_convolution(oalgpu_context *c, uint32_t slot, oalgpu_convolution *conv)
-{
-    if(!c || slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_convolution: bad slot");
-    if(conv && c->slotTarget[slot] >= 0 && ConvOutLines(conv) > c->L.wetChannels)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_convolution: the effect mixes into more lines than the wet bus of the slot's target has");
-    if(conv && c->slotTarget[slot] < 0 && ConvOutLines(conv) > c->L.numDry)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_convolution: the effect mixes into more lines than the context has dry lines");
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->slotConv[slot] = conv;
-    return OALGPU_OK;
-}
-
-static uint32_t AttachedReverbs(const oalgpu_context *c)
-{ return uint32_t(c->slotReverb.size() - std::count(c->slotReverb.begin(), c->slotReverb.end(), nullptr)); }
-
-// An EAX reverb instance is ONE workgroup that needs a compute unit's LDS nearly to itself (128 KB: both pipelines' rows,
-// csrc/reverb_kernels.hip), and it runs on the post stream beside the NEXT update's voice kernel.  A voice kernel whose grid fills
-// the machine exactly (two 78 KB workgroups on every CU) then finds the instances' CUs taken: the workgroups it cannot place wait
-// for a second round, and the launch lasts 1.6 times as long (BASELINE configs[3]: 110 -> 174 us in every other update, the
-// reverbs 85 -> 170 us in the updates between, profiles/r5/evidence/step_timeline_config4.txt).  With reverbs attached the
-// automatic voices-per-workgroup choice therefore leaves the instances their CUs: a few more voices per wavefront, so that the
-// grid fits on the CUs that are left -- one round, and the reverbs run beside it undisturbed.
-// voice_rows.hip's grid: one workgroup of eight wavefronts per compute unit -- the compute units the attached EAX reverb instances need
-// (a whole CU's LDS each, beside the NEXT update's voice kernel, see below) left out --, the voices dealt evenly
-static void SetRowsGroups(oalgpu_context *c)
-{
-    DeviceLayout &L = c->L;
-    const uint32_t reverbs = AttachedReverbs(c);
-    const uint32_t cus = DeviceComputeUnits(c->desc.device);
-    const uint32_t waves = RowsWavesPerGroup();
-    uint32_t groups = std::min<uint32_t>(cus > reverbs ? cus - reverbs : 1u, (L.numVoices + waves - 1u) / waves);
-    if(c->desc.voices_per_group) groups = (L.numVoices + c->desc.voices_per_group - 1u) / c->desc.voices_per_group;
-    groups = std::max<uint32_t>(1u, std::min<uint32_t>(groups, c->groupsAllocated));
-    L.rowsVpg = (L.numVoices + groups - 1u) / groups;
-    L.numGroups = (L.numVoices + L.rowsVpg - 1u) / L.rowsVpg;
-    L.numLineGroups = L.numGroups;
-}
-
-static int RebalanceWaveGroups(oalgpu_context *c)
-{
-    if(c->useWave && c->L.rows8)
-    {
-        const uint32_t before = c->L.rowsVpg;
-        DeviceLayout T = c->L;
-        SetRowsGroups(c);
-        if(c->L.rowsVpg != before)
-        {   // (the streams may still run launches of the old grid)
-            const DeviceLayout N = c->L;
-            c->L = T;
-            if(int rc = oalgpu_sync(c)) return rc;
-            c->L = N;
-        }
-        return OALGPU_OK;
-    }
-    if(!c->useWave || c->desc.voices_per_group != 0u || c->L.wave16) return OALGPU_OK;
-    const uint32_t reverbs = AttachedReverbs(c);
-    hipDeviceProp_t prop{};
-    if(hipGetDeviceProperties(&prop, c->desc.device) != hipSuccess || prop.multiProcessorCount <= 0) { (void)hipGetLastError(); return OALGPU_OK; }
-    const uint32_t cus = uint32_t(prop.multiProcessorCount);
-    const uint32_t slots = 2u * (cus > reverbs ? cus - reverbs : 1u);          // two voice workgroups per compute unit
-    DeviceLayout &L = c->L;
-    uint32_t vpw = std::max<uint32_t>(1u, (c->desc.max_voices + 2047u) / 2048u);  // (oalgpu_context_create's rule)
-    const uint32_t full = 2u * cus;
-    auto groupsOf = [&](uint32_t w) { DeviceLayout T = L; T.waveVoices = w; return WaveKernelGroups(T); };
-    // only a grid that was meant to fill the machine in one round is thinned out (smaller scenes leave room anyway)
-    if(reverbs && groupsOf(vpw) <= full) { while(groupsOf(vpw) > slots) ++vpw; }
-    if(vpw == L.waveVoices) return OALGPU_OK;
-    if(int rc = oalgpu_sync(c)) return rc;
-    L.waveVoices = vpw;
-    L.numGroups = std::max<uint32_t>(1u, WaveKernelGroups(L));       // (never more than the context's buffers were sized for)
-    L.numLineGroups = L.numGroups;
-    return OALGPU_OK;
-}
-
-int oalgpu_slot_set_effect(oalgpu_context *c, uint32_t slot, oalgpu_effect *fx)
-{
-    if(!c || slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_effect: bad slot");
-    // (a dedicated effect may address the real output lines, which follow the dry lines in the bus block)
-    // (on a slot with a target: the target's wet bus)
-    if(fx && (EffectOutLines(fx) > (c->slotTarget[slot] >= 0 ? c->L.wetChannels : c->L.numDry + c->L.numReal) || EffectInChannels(fx) > c->L.wetChannels))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_effect: the effect's lines do not fit the context's buses");
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->slotEffect[slot] = fx;
-    return OALGPU_OK;
-}
-
-int oalgpu_slot_set_reverb(oalgpu_context *c, uint32_t slot, oalgpu_reverb *rev)
-{
-    if(!c || slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: bad slot");
-    if(rev && c->L.wetChannels < 4)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: the reverb reads a 4-line B-Format wet bus");
-    if(rev && c->slotTarget[slot] >= 0 && ReverbOutLines(rev) > c->L.wetChannels)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: the effect mixes into more lines than the wet bus of the slot's target has");
-    if(rev && c->slotTarget[slot] < 0 && ReverbOutLines(rev) > c->L.numDry)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_set_reverb: the effect mixes into more lines than the context has dry lines");
-    if(int rc = oalgpu_sync(c)) return rc;
-    if(rev) { if(int rc = oalgpu_reverb_set_math_mode(rev, c->exact ? OALGPU_MATH_EXACT : OALGPU_MATH_FAST)) return rc; }
-    c->slotReverb[slot] = rev;
-    return RebalanceWaveGroups(c);
-}
-
-/* ---- effect slot targets: AL_EFFECTSLOT_TARGET_SOFT (al/auxeffectslot.cpp:504-520; alc/alu.cpp:627-632, :2220-2249) ---- */
-int oalgpu_slot_order(const int32_t *targets, uint32_t num_slots, uint32_t *order, uint32_t *depth)
-{
-    if(num_slots && (!targets || !order)) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_order: null argument");
-    if(!SlotOrder(targets, num_slots, order, depth))
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_order: a target out of range, a slot that targets itself, or a cycle");
-    return OALGPU_OK;
-}
-
-int oalgpu_slot_set_target(oalgpu_context *c, uint32_t slot, int32_t target_slot)
-{
-    const std::string w = "oalgpu_slot_set_target: ";
-    if(!c) return Fail(OALGPU_ERR_INVALID, w + "null context");
-    if(slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, w + "bad slot");
-    if(target_slot < -1 || target_slot >= int32_t(c->L.numSlots)) return Fail(OALGPU_ERR_INVALID, w + "the target is out of range (-1 .. num_slots - 1)");
-    if(target_slot == int32_t(slot)) return Fail(OALGPU_ERR_INVALID, w + "a slot cannot target itself");
-    std::vector<int32_t> targets = c->slotTarget;
-    targets[slot] = target_slot;
-    std::vector<uint32_t> order(c->L.numSlots), depth(c->L.numSlots);
-    if(!SlotOrder(targets.data(), c->L.numSlots, order.data(), depth.data()))
-        return Fail(OALGPU_ERR_INVALID, w + "the target would close a cycle");
-    if(target_slot >= 0 && (ConvOutLines(c->slotConv[slot]) > c->L.wetChannels || EffectOutLines(c->slotEffect[slot]) > c->L.wetChannels
-        || ReverbOutLines(c->slotReverb[slot]) > c->L.wetChannels))
-        return Fail(OALGPU_ERR_INVALID, w + "what is attached to the slot mixes into more lines than the target's wet bus has");
-    if(int rc = oalgpu_sync(c)) return rc;
-    c->slotTarget.swap(targets);
-    c->slotOrder.swap(order);
-    c->slotDepth.swap(depth);
-    return OALGPU_OK;
-}
-
-int oalgpu_slot_target(oalgpu_context *c, uint32_t slot, int32_t *target_slot)
-{
-    if(!c || !target_slot) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_target: null argument");
-    if(slot >= c->L.numSlots) return Fail(OALGPU_ERR_INVALID, "oalgpu_slot_target: bad slot");
-    *target_slot = c->slotTarget[slot];
-    return OALGPU_OK;
-}
-
 const char *oalgpu_voice_kernel_name(oalgpu_context *c)
 {
     if(!c) return "";
@@ -1328,57 +768,6 @@ const char *oalgpu_voice_kernel_name(oalgpu_context *c)
 
 /* Multi-GPU: whether this context's voice kernel continues the carried HRTF accumulator tail
  * (exactly one rank must, the one that runs the post-process on the reduced buses). */
-int oalgpu_resident_stats(oalgpu_context *c, oalgpu_resident_info *out)
-{
-    if(!c || !out) return Fail(OALGPU_ERR_INVALID, "null argument");
-    auto &R = c->res;
-    uint32_t w[kRcCount * 16] = {};
-    if(R.ready && !R.running)
-    {   // the wait counters: a copy on the null stream, with nothing resident on the device
-        if(int rc = UseDevice(c->desc.device)) return rc;
-        HIP_TRY(hipMemcpy(w, R.counters.p, sizeof(w), hipMemcpyDeviceToHost));
-    }
-    std::lock_guard<std::mutex> g(gResLock);
-    out->enabled = R.enabled ? 1 : 0; out->failed = R.failed ? 1 : 0; out->running = R.running ? 1 : 0;
-    out->door_in_device_memory = R.doorInBar ? 1 : 0;
-    out->launches = R.launches; out->updates = R.next; out->parks = uint32_t(R.parks);
-    out->timed_launches = uint32_t(R.kernelLaunches); out->timed_updates = R.kernelUpdates; out->timed_kernel_ms = R.kernelMs;
-    out->max_updates_per_launch = R.maxUpdates; out->pad = 0;
-    // (the voice kernel's words: every 128th workgroup keeps them)
-    const double tick = 0.01, groups = double(std::max<uint32_t>((c->L.numGroups + 127u) / 128u, 1u));
-    out->wait_door_us = w[16 * kRcWaitDoor] * tick / groups; out->wait_reduction_us = w[16 * kRcWaitRed] * tick / groups;
-    out->wait_arrival_us = w[16 * kRcWaitArrive] * tick; out->wait_post_us = w[16 * kRcWaitPost] * tick;
-    out->wait_reduced_us = w[16 * kRcWaitRedDone] * tick; out->wait_split_us = w[16 * kRcWaitSplit] * tick;
-    out->install_us = w[16 * kRcInstall] * tick / groups; out->busy_us = w[16 * kRcBusy] * tick / groups;
-    out->top_us = w[16 * kRcTop] * tick / groups;
-    return OALGPU_OK;
-}
-
-int oalgpu_resident_set_short_run(oalgpu_context *c, uint32_t updates)
-{
-    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
-    if(int rc = UseCtx(c)) return rc;
-    c->res.shortRun = updates;
-    c->res.shortRuns = 0; c->res.cooldown = 0;
-    return OALGPU_OK;
-}
-
-int oalgpu_resident_set_timing(oalgpu_context *c, int enable)
-{
-    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
-    if(int rc = UseCtx(c)) return rc;           // (the running launch ends: the next one carries the events, or no longer does)
-    c->res.timeLaunches = enable != 0;
-    return OALGPU_OK;
-}
-
-int oalgpu_resident_set_max_updates(oalgpu_context *c, uint32_t max_updates)
-{
-    if(!c || max_updates == 0 || max_updates > 0x10000000u) return Fail(OALGPU_ERR_INVALID, "oalgpu_resident_set_max_updates: 1 .. 2^28");
-    if(int rc = UseCtx(c)) return rc;
-    c->res.maxUpdates = max_updates;
-    return OALGPU_OK;
-}
-
 int oalgpu_set_carry_accum(oalgpu_context *c, int enable)
 {
     if(int rc = BeginSetter(c, "oalgpu_set_carry_accum")) return rc;

@@ -1,4 +1,5 @@
-// The device context and what the C-ABI translation units share (api.hip: context life, the update, slots; api_comm.hip: the
+// The device context and what the C-ABI translation units share (api.hip: context life, the update; api_resident.hip: the
+// resident voice kernel's host side; api_attach.hip: several contexts on one device; api_slots.hip: the effect slots; api_comm.hip: the
 // sharded update's transports; api_percall.hip: the per-call operators; api_hrtf.hip: HRTF data sets; api_buffers.hip: buffer handles;
 // api_voices.hip: voices, parameters; api_output.hip: what comes back; api_poststage.hip: what is installed and run behind the buses; api_callback.hip:
 // callback sources).  Host logic only; no CPU fallback anywhere.
@@ -85,6 +86,17 @@ inline const TableBlob &Blob() { static const TableBlob b; return b; }
 // context.  Stabilizer and Bs2b decode with the B-Format decoder installed under them; HRTF contexts are DeviceLayout::hrtf.
 enum class PostKind : uint32_t { None, AmbiDec, Stabilizer, Bs2b, Uhj, Tsme };
 
+// One effect slot: what is attached to it (not owned; each may be null) and where its effects add into.  target: the slot whose
+// wet bus that is (oalgpu_slot_set_target: AL_EFFECTSLOT_TARGET_SOFT, alc/alu.cpp:627-632 and :2220-2249), -1: the device's lines;
+// depth: what host/slot_order.cpp makes of the graph -- recomputed when a target changes, read by RunEffects (api_slots.hip)
+struct EffectSlot {
+    oalgpu_convolution *conv{nullptr};     // convolution reverb
+    oalgpu_reverb *reverb{nullptr};        // EAX reverb
+    oalgpu_effect *effect{nullptr};        // equalizer / modulator / echo / dedicated
+    int32_t target{-1};
+    uint32_t depth{0};
+};
+
 struct BusTransport;
 struct oalgpu_context {
     oalgpu_context_desc desc{};
@@ -156,15 +168,9 @@ struct oalgpu_context {
     bool carryAccum{true};
     bool useWave{false};                   // FAST contexts without sends (HRTF, or <= 8 dry lines): voice_wave.hip
     uint32_t groupsAllocated{0};           // workgroups the partial-bus buffers were sized for (oalgpu_context_create)
-    std::vector<oalgpu_convolution*> slotConv;   // per effect slot: attached convolution reverb (not owned)
-    std::vector<oalgpu_reverb*> slotReverb;      // per effect slot: attached EAX reverb (not owned)
-    std::vector<oalgpu_effect*> slotEffect;      // per effect slot: equalizer / modulator / echo / dedicated (not owned)
+    std::vector<EffectSlot> slots;               // per effect slot
+    std::vector<uint32_t> slotOrder;             // the order RunEffects goes through them: a permutation, by descending depth
     DevBuf<uint32_t> reverbTicket;               // mix-out order word of a reverb batch launch
-    // effect slot targets (oalgpu_slot_set_target: AL_EFFECTSLOT_TARGET_SOFT, alc/alu.cpp:627-632 and :2220-2249): slot -> the slot
-    // whose wet bus its effects add into (-1: the device's lines), and what host/slot_order.cpp makes of the graph -- recomputed
-    // when a target changes, read by RunEffects
-    std::vector<int32_t> slotTarget;
-    std::vector<uint32_t> slotOrder, slotDepth;
 
     DevBuf<float> tables;
     DevBuf<BufferItem> buffers;
@@ -292,7 +298,6 @@ struct oalgpu_context {
         bool enabled{false};                       // the context was created with OALGPU_CTX_RESIDENT and its layout has a resident kernel
         bool ready{false}, failed{false};          // buffers and streams exist; the mode gave up (the context then launches per update)
         bool running{false};                       // a launch is on the main stream that has not been told to leave
-        std::mutex lock;                           // submit / park (another context's entry point parks this one's kernel)
         hipStream_t reduceStream{nullptr};
         ResidentDoor *door{nullptr};               // the host's view (the device reads the same address)
         bool doorInBar{false};
@@ -386,9 +391,28 @@ namespace oalgpu { extern thread_local std::string gLastError; }
 
 // ---- shared between the translation units (definitions: api.hip unless noted) ----
 int FlushPendingMix(oalgpu_context *c, struct oalgpu_param_block *next = nullptr);
+int UseCtx(oalgpu_context *c);
+// the update's pieces that other units launch: a context's voices and reduction on its main stream (oalgpu_mix_voices; what a
+// device context does for each attached context), the carried accumulator a reduction adds, the one-launch HRTF post-process
+int MixVoicesSerial(oalgpu_context *c, uint32_t samples_to_do);
+const float *CarrySource(oalgpu_context *c, bool carry);
+int PostDirectHrtfFused(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do, hipEvent_t evDone, bool resident = false);
+int RebalanceWaveGroups(oalgpu_context *c);                        // (the voice kernel's grid, after a reverb came or went)
+// the resident voice kernel's host side (api_resident.hip)
+namespace oalgpu { void ParkResidentContexts(int device); }
 bool ResidentWanted(const oalgpu_context *c, int post_process);
 int FlushResidentBlock(oalgpu_context *c);
-int UseCtx(oalgpu_context *c);
+int ResidentSubmit(oalgpu_context *c, uint32_t samples_to_do);     // 1: the update goes the launched way after all
+void ResidentCollectTimes(oalgpu_context *c, bool all);
+int ResidentCheckError(oalgpu_context *c);
+// several contexts on one device (api_attach.hip)
+int RefuseAttached(const oalgpu_context *c, const char *who);
+int MixAttached(oalgpu_context *c, uint32_t samples_to_do);
+int MergeAttached(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do);
+void DetachForDestroy(oalgpu_context *ctx);
+// the effect slots (api_slots.hip)
+int RunEffects(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do);
+uint32_t AttachedReverbs(const oalgpu_context *c);
 int UseCtxResident(oalgpu_context *c);
 void RetireCallbackVoice(oalgpu_context *c, uint32_t voice);
 void NoteCallbackSteps(oalgpu_context *c, const uint32_t *voices, const oalgpu_voice_params *params, size_t count);

@@ -1,4 +1,4 @@
-// Small host-side helpers shared by the C-ABI translation units (api.hip, conv_api.hip).
+// Small host-side helpers shared by the C-ABI translation units (api.hip and its api_*.hip siblings, conv_api.hip, reverb_api.hip, effects_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

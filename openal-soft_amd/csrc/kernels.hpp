@@ -303,23 +303,25 @@ void LaunchPostDirectHrtfFast(hipStream_t s, float *left, float *right, const fl
 // the same as ONE launch (pipelined FAST HRTF contexts): see post_wave.hip
 // workgroups of the reduction inside LaunchReducePostFused: 64 bus columns each (BusFloats(L) / 64, rounded up)
 inline uint32_t ReducePostReduceGroups(const DeviceLayout &L) { return uint32_t((BusFloats(L) + 63u) / 64u); }
-void LaunchReducePostFused(hipStream_t s, const DeviceLayout &L, const float *carry, float *left, float *right, const float *in, uint32_t nch,
-    const float *accIn, float *carryOut, const SplitterState *spIn, SplitterState *spOut, const float *hfscales, const float *chanCoeffs,
-    uint32_t irsize, uint32_t n, float *xf, uint32_t *arrived, uint32_t epoch, const float runPower[4], hipEvent_t evDone,
-    float *hostOut, uint32_t *hostFlag, uint32_t hostSeq, uint32_t *outArrived, uint32_t outTarget, uint32_t *reduced, uint32_t reducedEpoch);
-void LaunchPostDirectHrtfFused(hipStream_t s, float *left, float *right, const float *in, uint32_t nch, const float *accIn, float *carryOut,
-    const SplitterState *spIn, SplitterState *spOut, const float *hfscales, const float *chanCoeffs, uint32_t irsize, uint32_t n,
-    float *xf, uint32_t *arrived, uint32_t epoch, const float runPower[4], hipEvent_t evDone = nullptr,
-    float *hostOut = nullptr, uint32_t *hostFlag = nullptr, uint32_t hostSeq = 0, uint32_t *outArrived = nullptr, uint32_t outTarget = 0);
+// what the three one-launch forms take alike (PostDirectHrtfFused, api.hip, fills it once per update): the two output lines, the
+// bus block's dry channels, the accumulator in and out, the splitter states in and out, the decoder, the update's length, the
+// scratch, the channel counter and its epoch, the splitters' run powers, the launch's event and the host's ring slot
+struct PostHrtfCall {
+    float *left, *right; const float *in; uint32_t nch; const float *accIn; float *carryOut;
+    const SplitterState *spIn; SplitterState *spOut; const float *hfscales, *chanCoeffs; uint32_t irsize, n;
+    float *xf; uint32_t *arrived; uint32_t epoch; const float *runPower; hipEvent_t evDone;
+    float *hostOut; uint32_t *hostFlag; uint32_t hostSeq;
+};
+void LaunchReducePostFused(hipStream_t s, const PostHrtfCall &p, const DeviceLayout &L, const float *carry, uint32_t *outArrived, uint32_t outTarget,
+    uint32_t *reduced, uint32_t reducedEpoch);
+void LaunchPostDirectHrtfFused(hipStream_t s, const PostHrtfCall &p, uint32_t *outArrived, uint32_t outTarget);
 // resident contexts (OALGPU_CTX_RESIDENT): the reduction and the post-process of one update as launches that wait for device
 // counters instead of for the voice kernel's end (post_wave.hip)
 void LaunchBusReduceResident(hipStream_t s, const DeviceLayout &L, const float *carry, uint32_t *counters, uint32_t *hostFlags, uint32_t set,
     uint32_t arriveTarget, uint32_t postDoneTarget);
 uint32_t PostResidentFirGroups();
-void LaunchPostResident(hipStream_t s, float *left, float *right, const float *in, uint32_t nch, const float *accIn, float *carryOut,
-    const SplitterState *spIn, SplitterState *spOut, const float *hfscales, const float *chanCoeffs, uint32_t irsize, uint32_t n,
-    float *xf, uint32_t *arrived, uint32_t epoch, const float runPower[4], hipEvent_t evDone, float *hostOut, uint32_t *hostFlag, uint32_t hostSeq,
-    uint32_t *counters, uint32_t *hostFlags, uint32_t redDoneTarget, uint32_t postDoneTarget, uint32_t progressValue);
+void LaunchPostResident(hipStream_t s, const PostHrtfCall &p, uint32_t *counters, uint32_t *hostFlags, uint32_t redDoneTarget, uint32_t postDoneTarget,
+    uint32_t progressValue);
 
 // ---- launchers (output_kernels.hip): BFormatDec, ApplyDither, Write<T> behind the buses ----
 // gainsHf / gainsLf: [dry line][32] (column = output line); gainsLf null = single-band decoder; bands =

@@ -464,56 +464,51 @@ void LaunchBusReduceResident(hipStream_t s, const DeviceLayout &L, const float *
     hipLaunchKernelGGL(BusReduceResidentKernel, dim3((total + 63u) / 64u), dim3(256), 0, s, L, carry, ResidentReduceArgs{counters, hostFlags, set, arriveTarget, postDoneTarget});
 }
 
+// what the kernels take in place of a PostHrtfCall's irsize and runPower
+static uint32_t PostTaps(uint32_t irsize) { return irsize <= 16u ? 16u : ((irsize + 15u) & ~15u); }
+static Tri3 PostRunPower(const PostHrtfCall &p) { return Tri3{p.runPower[0], p.runPower[1], p.runPower[2], p.runPower[3]}; }
+
 // update u's HRTF post-process of a resident context (PostFusedBlock<2>); redDoneTarget: what kRcRedDone reads when update u's
 // reduction is through; postDoneTarget: what kRcPostDone reads when this launch's FIR workgroups are; progressValue: what the
 // last of them stores into the host's progress word
 uint32_t PostResidentFirGroups() { return uint32_t(kPostFrames / kFusedFrames); }
-void LaunchPostResident(hipStream_t s, float *left, float *right, const float *in, uint32_t nch, const float *accIn, float *carryOut,
-    const SplitterState *spIn, SplitterState *spOut, const float *hfscales, const float *chanCoeffs, uint32_t irsize, uint32_t n,
-    float *xf, uint32_t *arrived, uint32_t epoch, const float runPower[4], hipEvent_t evDone, float *hostOut, uint32_t *hostFlag, uint32_t hostSeq,
-    uint32_t *counters, uint32_t *hostFlags, uint32_t redDoneTarget, uint32_t postDoneTarget, uint32_t progressValue)
+void LaunchPostResident(hipStream_t s, const PostHrtfCall &p, uint32_t *counters, uint32_t *hostFlags, uint32_t redDoneTarget, uint32_t postDoneTarget,
+    uint32_t progressValue)
 {
-    const uint32_t taps = irsize <= 16u ? 16u : ((irsize + 15u) & ~15u);
-    const Tri3 P{runPower[0], runPower[1], runPower[2], runPower[3]};
     const PostResident PR{counters + 16u * kRcPostDone, postDoneTarget, hostFlags + 16u * kRhProgress, progressValue, hostFlags + 16u * kRhError, counters};
-    hipExtLaunchKernelGGL(PostResidentKernel, dim3(nch + kPostFrames / kFusedFrames), dim3(64), 0, s, nullptr, evDone, 0u, in, nch, spIn, spOut, hfscales,
-        chanCoeffs, taps, accIn, carryOut, left, right, n, xf, arrived, epoch, P, hostOut, hostFlag, hostSeq, counters + 16u * kRcRedDone, redDoneTarget, PR);
+    hipExtLaunchKernelGGL(PostResidentKernel, dim3(p.nch + kPostFrames / kFusedFrames), dim3(64), 0, s, nullptr, p.evDone, 0u, p.in, p.nch, p.spIn, p.spOut,
+        p.hfscales, p.chanCoeffs, PostTaps(p.irsize), p.accIn, p.carryOut, p.left, p.right, p.n, p.xf, p.arrived, p.epoch, PostRunPower(p), p.hostOut,
+        p.hostFlag, p.hostSeq, counters + 16u * kRcRedDone, redDoneTarget, PR);
 }
 
-// the whole FAST post-process in one launch; spIn / spOut: the two splitter-state buffers of the context (the caller swaps them),
-// carryOut: the carried accumulator the next reduction adds (1152 x 2); xf: nch x 1024 floats of scratch; arrived / epoch: the
-// context's channel counter and the value it reaches when this update's channels are all there (nch more than before);
-// runPower: the splitter's transition over a run of ((n + 63) / 64) | 1 samples as the scan wants it (SplitterRunPowers, api.hip);
-// hostOut (null: none): 2 x 1024 floats of pinned host memory that receive the two output lines, hostFlag: where hostSeq is
-// stored when they are all there, outArrived / outTarget: the context's counter of FIR workgroups (it only ever grows) and what
-// it reads when this launch's are all through
-void LaunchPostDirectHrtfFused(hipStream_t s, float *left, float *right, const float *in, uint32_t nch, const float *accIn, float *carryOut,
-    const SplitterState *spIn, SplitterState *spOut, const float *hfscales, const float *chanCoeffs, uint32_t irsize, uint32_t n,
-    float *xf, uint32_t *arrived, uint32_t epoch, const float runPower[4], hipEvent_t evDone,
-    float *hostOut, uint32_t *hostFlag, uint32_t hostSeq, uint32_t *outArrived, uint32_t outTarget)
+// the whole FAST post-process in one launch (PostHrtfCall, kernels.hpp); spIn / spOut: the two splitter-state buffers of the
+// context (the caller swaps them), carryOut: the carried accumulator the next reduction adds (1152 x 2); xf: nch x 1024 floats of
+// scratch; arrived / epoch: the context's channel counter and the value it reaches when this update's channels are all there
+// (nch more than before); runPower: the splitter's transition over a run of ((n + 63) / 64) | 1 samples as the scan wants it
+// (SplitterRunPowers, api.hip); hostOut (null: none): 2 x 1024 floats of pinned host memory that receive the two output lines,
+// hostFlag: where hostSeq is stored when they are all there, outArrived / outTarget: the context's counter of FIR workgroups (it
+// only ever grows) and what it reads when this launch's are all through
+void LaunchPostDirectHrtfFused(hipStream_t s, const PostHrtfCall &p, uint32_t *outArrived, uint32_t outTarget)
 {
-    const uint32_t taps = irsize <= 16u ? 16u : ((irsize + 15u) & ~15u);
-    const Tri3 P{runPower[0], runPower[1], runPower[2], runPower[3]};
     static_assert(kPostFrames % kFusedFrames == 0, "whole workgroups");
-    hipExtLaunchKernelGGL(PostFusedKernel, dim3(nch + kPostFrames / kFusedFrames), dim3(64), 0, s, nullptr, evDone, 0u, in, nch, spIn, spOut, hfscales,
-        chanCoeffs, taps, accIn, carryOut, left, right, n, xf, arrived, epoch, P, hostOut, hostFlag, hostSeq, outArrived, outTarget);
+    hipExtLaunchKernelGGL(PostFusedKernel, dim3(p.nch + kPostFrames / kFusedFrames), dim3(64), 0, s, nullptr, p.evDone, 0u, p.in, p.nch, p.spIn, p.spOut,
+        p.hfscales, p.chanCoeffs, PostTaps(p.irsize), p.accIn, p.carryOut, p.left, p.right, p.n, p.xf, p.arrived, p.epoch, PostRunPower(p), p.hostOut,
+        p.hostFlag, p.hostSeq, outArrived, outTarget);
 }
 
 // The reduction of update k and its HRTF post-process in one launch (see ReducePostFusedKernel); reduced / reducedEpoch: the
 // context's counter of reduction workgroups and what it reads when this update's are all through
-void LaunchReducePostFused(hipStream_t s, const DeviceLayout &L, const float *carry, float *left, float *right, const float *in, uint32_t nch,
-    const float *accIn, float *carryOut, const SplitterState *spIn, SplitterState *spOut, const float *hfscales, const float *chanCoeffs,
-    uint32_t irsize, uint32_t n, float *xf, uint32_t *arrived, uint32_t epoch, const float runPower[4], hipEvent_t evDone,
-    float *hostOut, uint32_t *hostFlag, uint32_t hostSeq, uint32_t *outArrived, uint32_t outTarget, uint32_t *reduced, uint32_t reducedEpoch)
+void LaunchReducePostFused(hipStream_t s, const PostHrtfCall &p, const DeviceLayout &L, const float *carry, uint32_t *outArrived, uint32_t outTarget,
+    uint32_t *reduced, uint32_t reducedEpoch)
 {
     ReducePostArgs A{};
     A.carry = carry; A.nReduce = ReducePostReduceGroups(L);
-    A.in = in; A.nch = nch; A.spIn = spIn; A.spOut = spOut; A.hfscales = hfscales; A.chanCoeffs = chanCoeffs;
-    A.taps = irsize <= 16u ? 16u : ((irsize + 15u) & ~15u);
-    A.accIn = accIn; A.carryOut = carryOut; A.left = left; A.right = right; A.n = n; A.xf = xf; A.arrived = arrived; A.epoch = epoch;
-    A.runPower = Tri3{runPower[0], runPower[1], runPower[2], runPower[3]};
-    A.hostOut = hostOut; A.hostFlag = hostFlag; A.hostSeq = hostSeq; A.outArrived = outArrived; A.outTarget = outTarget; A.reduced = reduced; A.reducedEpoch = reducedEpoch;
-    hipExtLaunchKernelGGL(ReducePostFusedKernel, dim3(A.nReduce + nch + kPostFrames / kFusedFrames), dim3(256), 0, s, nullptr, evDone, 0u, L, A);
+    A.in = p.in; A.nch = p.nch; A.spIn = p.spIn; A.spOut = p.spOut; A.hfscales = p.hfscales; A.chanCoeffs = p.chanCoeffs;
+    A.taps = PostTaps(p.irsize);
+    A.accIn = p.accIn; A.carryOut = p.carryOut; A.left = p.left; A.right = p.right; A.n = p.n; A.xf = p.xf; A.arrived = p.arrived; A.epoch = p.epoch;
+    A.runPower = PostRunPower(p);
+    A.hostOut = p.hostOut; A.hostFlag = p.hostFlag; A.hostSeq = p.hostSeq; A.outArrived = outArrived; A.outTarget = outTarget; A.reduced = reduced; A.reducedEpoch = reducedEpoch;
+    hipExtLaunchKernelGGL(ReducePostFusedKernel, dim3(A.nReduce + p.nch + kPostFrames / kFusedFrames), dim3(256), 0, s, nullptr, p.evDone, 0u, L, A);
 }
 
 // temp: nch x 1024 filtered channels, then 1152 x 2 channel sums
@@ -522,7 +517,7 @@ void LaunchPostDirectHrtfFast(hipStream_t s, float *left, float *right, const fl
     SplitterState *splitters, const float *hfscales, const float *chanCoeffs, uint32_t irsize, uint32_t n, float *temp, hipEvent_t evDone)
 {
     float *xf = temp, *tmp = temp + size_t{nch} * kLine;
-    const uint32_t taps = irsize <= 16u ? 16u : ((irsize + 15u) & ~15u);
+    const uint32_t taps = PostTaps(irsize);
     hipLaunchKernelGGL(PostSplitKernel, dim3(nch), dim3(64), 0, s, in, xf, splitters, hfscales, n);
     // (16 frames per workgroup: 47.5 us per step against 49.0 with 8 and 50.5 with round 2's single workgroup, one box)
     hipLaunchKernelGGL(PostFirKernel<16>, dim3(kPostFrames / 16), dim3(64), 0, s, xf, nch, chanCoeffs, taps, tmp);

@@ -64,7 +64,7 @@ void LaunchReverbInstall(hipStream_t s, oalgpu_reverb_pipeline *dst, const oalgp
 
 } // namespace oalgpu
 
-// api.hip: process `count` reverbs (<= kRvBatchMax) that share a stream as one launch, instance i adding into
+// api_slots.hip (RunEffects): process `count` reverbs (<= kRvBatchMax) that share a stream as one launch, instance i adding into
 // out_lines_dev[i] (the same block for the instances of slots with the same destination; a slot with a target: that
 // slot's wet bus); `ticket_dev` is a zeroed device word owned by the caller
 int oalgpu_reverb_process_batch_device(oalgpu_reverb *const *revs, const float *const *wet_in_dev, uint32_t count,
