@@ -458,6 +458,85 @@ void oalgpu_param_block_destroy(oalgpu_param_block *block);
 /* ProcessVoiceChanges side (alc/alu.cpp:2057-2151): Playing / Stopping / Stopped. */
 int oalgpu_voice_set_state(oalgpu_context *ctx, uint32_t voice, int play_state);
 
+/* ---- 3D source parameters on the GPU: CalcAttnVoiceParams + CalcPanningAndFilters --------------------------------
+ * For a MONO 3D POINT SOURCE (FmtMono, !mPanningEnabled, spatialize mode on or auto) the library computes what
+ * CalcAttnVoiceParams (alc/alu.cpp:1712-2010) and CalcPanningAndFilters (:1512-1657) leave in the Voice -- listener
+ * transform, distance model, cone, gain clamps, air absorption, wet decay, Doppler, mStep, PrepareResampler, spread, the
+ * 2 + 12 shelf designs, the HRTF direction (getCoeffs) or the pan gains -- from the source's properties, in ONE kernel
+ * (SourceParamsKernel, csrc/source_kernels.hip) that writes the records oalgpu_voice_set_params would have built on the
+ * host.  Integers (mStep, resampler state, FilterActive, send slots) equal the reference's bit for bit; what passes
+ * through pow / acos / asin / atan2 / sin / cos is within the device math library's error of glibc's.
+ *
+ * oalgpu_listener_params: ContextParams (core/context.h:67-84) and alu.cpp's file-scope scales.  matrix: Matrix, row
+ * major as al::Matrix (common/vecmat.h:80-121: out[c] = sum_r vec[r] * matrix[r*4 + c]); position: Position (w = 1);
+ * velocity: Velocity (already rotated, alu.cpp:533); gain: Gain; meters_per_unit: MetersPerUnit; air_absorption_gain_hf:
+ * AirAbsorptionGainHF; doppler_factor: DopplerFactor; speed_of_sound: SpeedOfSound; source_distance_model:
+ * SourceDistanceModel; distance_model: mDistanceModel (oalgpu_distance_model); cone_scale: ConeScale (alu.cpp:92-104);
+ * nfc_scale: NfcScale (:114); xyz_scale: XScale, YScale, ZScale (:109-111).  A context starts with ContextParams{}:
+ * identity, zero vectors, 1, 1, 0.99426, 1, 343.3, 0, Disable -- and 1, 1, {1, 1, 1}. */
+enum oalgpu_distance_model {            /* DistanceModel, core/context.h:36-43 */
+    OALGPU_DISTANCE_DISABLE, OALGPU_DISTANCE_INVERSE, OALGPU_DISTANCE_INVERSE_CLAMPED, OALGPU_DISTANCE_LINEAR,
+    OALGPU_DISTANCE_LINEAR_CLAMPED, OALGPU_DISTANCE_EXPONENT, OALGPU_DISTANCE_EXPONENT_CLAMPED
+};
+typedef struct oalgpu_listener_params {
+    float matrix[16], position[3], velocity[3];
+    float gain, meters_per_unit, air_absorption_gain_hf, doppler_factor, speed_of_sound;
+    int32_t source_distance_model, distance_model;
+    float cone_scale, nfc_scale, xyz_scale[3];
+} oalgpu_listener_params;
+int oalgpu_context_set_listener(oalgpu_context *ctx, const oalgpu_listener_params *listener);
+
+/* What CalcAttnVoiceParams reads from a send's EffectSlotBase (alu.cpp:1726, :1737, :1932-1939): active = EffectType !=
+ * EffectSlotType::None (a send into an inactive or absent slot has no buffer: send_slot -1), RoomRolloff, DecayTime,
+ * AirAbsorptionGainHF.  A slot starts inactive. */
+int oalgpu_slot_set_send_environment(oalgpu_context *ctx, uint32_t slot, int32_t active, float room_rolloff, float decay_time,
+    float air_absorption_gain_hf);
+
+/* The VoiceProps (core/voice.h:101-158) the two functions read for this source kind, in VoiceProps' order. */
+typedef struct oalgpu_source_send {     /* VoiceProps::SendData, core/voice.h:149-156 */
+    int32_t slot;                       /* Slot: the effect slot's index, -1 = none */
+    float gain, gain_hf, hf_reference, gain_lf, lf_reference;   /* Gain, GainHF, HFReference, GainLF, LFReference */
+} oalgpu_source_send;
+typedef struct oalgpu_source_props {
+    float pitch, gain, outer_gain, min_gain, max_gain;          /* Pitch, Gain, OuterGain, MinGain, MaxGain (:102-106) */
+    float inner_angle, outer_angle;                             /* InnerAngle, OuterAngle, degrees (:107-108) */
+    float ref_distance, max_distance, rolloff_factor;           /* RefDistance, MaxDistance, RolloffFactor (:109-111) */
+    float position[3], velocity[3], direction[3];               /* Position, Velocity, Direction (:112-114) */
+    int32_t head_relative;                                      /* HeadRelative (:117) */
+    int32_t distance_model;                                     /* mDistanceModel (:118), oalgpu_distance_model */
+    int32_t resampler;                                          /* mResampler (:119), oalgpu_resampler */
+    int32_t dry_gain_hf_auto, wet_gain_auto, wet_gain_hf_auto;  /* DryGainHFAuto, WetGainAuto, WetGainHFAuto (:124-126) */
+    float outer_gain_hf;                                        /* OuterGainHF (:127) */
+    float air_absorption_factor, room_rolloff_factor, doppler_factor;   /* (:129-131) */
+    float radius;                                               /* Radius (:135) */
+    float direct_gain, direct_gain_hf, direct_hf_reference, direct_gain_lf, direct_lf_reference;   /* Direct (:140-147) */
+    oalgpu_source_send send[OALGPU_MAX_SENDS];                  /* Send (:157) */
+} oalgpu_source_props;
+
+/* The synchronous form, like oalgpu_voice_set_params: voices[i] <- what the two functions make of props[i] under the
+ * listener and the slot environments as they are now; the voice's frequency is the one of its oalgpu_voice_desc.  Of two
+ * records of one voice the last wins.  OALGPU_ERR_INVALID, with nothing changed: a null argument, a voice index, a
+ * resampler, a distance model or a send slot out of range; a callback voice (its mStep is mirrored on the host); a context
+ * with near-field control (oalgpu_context_set_nfc: the per-voice w0 adjust stays host-side).  OALGPU_ERR_NO_HRTF: an HRTF
+ * context without a data set. */
+int oalgpu_voice_set_source_props(oalgpu_context *ctx, const uint32_t *voices, const oalgpu_source_props *props, size_t count);
+/* The same into an ordinary oalgpu_param_block (oalgpu_param_block_apply, oalgpu_mix_update_run), with the listener and the
+ * slot environments as they are at creation time; of two records of one voice the block keeps the last.  Refuses what
+ * oalgpu_voice_set_source_props refuses. */
+int oalgpu_param_block_create_from_sources(oalgpu_context *ctx, const uint32_t *voices, const oalgpu_source_props *props,
+    size_t count, oalgpu_param_block **out);
+/* The same arithmetic compiled for the host (glibc's libm; no device needed): out[i] <- props[i] for a context of `desc`
+ * (sample_rate, num_dry_channels, num_aux_sends, num_slots, wet_channels, hrtf) whose sources all have `frequency`.
+ * slots: desc->num_slots environments (NULL: all inactive); dry_index / dry_scale: the dry bus's AmbiMap, wet_index /
+ * wet_scale: num_slots x wet_channels (NULL: the identity, as in a fresh context); mhr: the HRTF context's data set (brought
+ * to desc->sample_rate).  out[i].dry_gains / send_gains are the resolved line gains; hrtf_dist is infinite for a source at
+ * the listener (alu.cpp:1296). */
+typedef struct oalgpu_slot_environment { int32_t active; float room_rolloff, decay_time, air_absorption_gain_hf; } oalgpu_slot_environment;
+int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
+    const oalgpu_slot_environment *slots, const uint8_t *dry_index, const float *dry_scale, const uint8_t *wet_index,
+    const float *wet_scale, const void *mhr, size_t mhr_size, uint32_t frequency, const oalgpu_source_props *props,
+    size_t count, oalgpu_voice_params *out);
+
 /* One update: zero the dry/real and wet buses, mix every Playing|Stopping voice
  * (Voice::mix, core/voice.cpp:988-1233), and -- HRTF context, post_process != 0 -- run
  * MixDirectHrtf over the dry bus (DeviceBase::Process(HrtfPostProcess), alc/alu.cpp:289-298).

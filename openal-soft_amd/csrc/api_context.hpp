@@ -1,7 +1,7 @@
 // The device context and what the C-ABI translation units share (api.hip: context life, the update; api_resident.hip: the
 // resident voice kernel's host side; api_attach.hip: several contexts on one device; api_slots.hip: the effect slots; api_comm.hip: the
 // sharded update's transports; api_percall.hip: the per-call operators; api_hrtf.hip: HRTF data sets; api_buffers.hip: buffer handles;
-// api_voices.hip: voices, parameters; api_output.hip: what comes back; api_poststage.hip: what is installed and run behind the buses; api_callback.hip:
+// api_voices.hip: voices, parameters; api_sources.hip: 3D source parameters computed on the GPU; api_output.hip: what comes back; api_poststage.hip: what is installed and run behind the buses; api_callback.hip:
 // callback sources).  Host logic only; no CPU fallback anywhere.
 #pragma once
 #include "../../include/oalgpu.h"
@@ -39,6 +39,7 @@
 #include "../host/tables.hpp"
 #include "api_util.hpp"
 #include "kernels.hpp"
+#include "dev_source.hpp"
 #include "bus_merge.hpp"
 #include "reverb_dev.hpp"
 
@@ -272,6 +273,18 @@ struct oalgpu_context {
     std::vector<ParamRecord> paramHost;
     DevBuf<VoiceInitRecord> initDev;
     std::vector<VoiceInitRecord> initPending;
+    // 3D source parameters on the GPU (api_sources.hip): ContextParams and alu.cpp's scales, what CalcAttnVoiceParams reads of
+    // every effect slot (host copy and device copy), the resampler tables' constants (uploaded with the first use), each voice
+    // slot's Voice::mFrequency (0: not started through oalgpu_voice_init), and the source records' staging
+    oalgpu_listener_params listener{{1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f}, {}, {},
+        1.0f, 1.0f, 0.99426f, 1.0f, 343.3f, 0, OALGPU_DISTANCE_DISABLE, 1.0f, 1.0f, {1.0f, 1.0f, 1.0f}};
+    std::vector<oalgpu_slot_environment> slotEnvHost;
+    DevBuf<oalgpu_slot_environment> slotEnv;
+    DevBuf<ResamplerConsts> rsConsts;
+    std::vector<uint32_t> voiceFreq;
+    DevBuf<SourceRecord> srcDev;
+    std::vector<SourceRecord> srcHost;
+    std::vector<uint32_t> srcVoices;        // (the voices of srcHost: a voice named twice keeps its last record)
     // callback sources (oalgpu_voice_init_callback): the host's mirror of what Voice::mix keeps for them
     struct CbVoice {
         uint32_t voice{0}; int32_t buffer{-1}; uint32_t frameBytes{4}, capacityFrames{0};
@@ -438,6 +451,8 @@ void FreeStorage(const std::vector<void*> &freed);
 inline bool VoiceOk(const oalgpu_context *c, uint32_t voice) { return c && voice < c->L.numVoices; }
 int BeginVoiceCall(oalgpu_context *c, bool argsOk = true, const char *who = "", bool sync = false);
 void PendStart(oalgpu_context *c, const VoiceInitRecord &rec);
+// a parameter block whose records are in place: its voice -> record map and, where the voice kernel installs blocks, its rows
+int FinishParamBlock(oalgpu_context *c, struct oalgpu_param_block *b, const uint32_t *voices, size_t count);
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip
 int ServiceCallbacks(oalgpu_context *c, uint32_t samplesToDo);     // api_callback.hip
 int CommReduceBus(oalgpu_context *c, hipStream_t s);               // api_comm.hip

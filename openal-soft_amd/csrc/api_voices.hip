@@ -48,13 +48,19 @@ int oalgpu_voice_init(oalgpu_context *c, uint32_t voice, const oalgpu_voice_desc
 {
     const oalgpu_voice_desc none{-1, 0, 0, 0u, 0u};             // (a null description names no buffer)
     if(!d) d = &none;
-    return StartVoice(c, "oalgpu_voice_init", false, voice, d->buffer, d->looping, d->position, d->position_frac);
+    if(int rc = StartVoice(c, "oalgpu_voice_init", false, voice, d->buffer, d->looping, d->position, d->position_frac)) return rc;
+    // Voice::mFrequency: what the source stage scales the pitch by (oalgpu_voice_set_source_props)
+    if(c->voiceFreq.size() < c->L.numVoices) c->voiceFreq.resize(c->L.numVoices, 0u);
+    c->voiceFreq[voice] = d->frequency;
+    return OALGPU_OK;
 }
 
 int oalgpu_voice_init_queue(oalgpu_context *c, uint32_t voice, int first_buffer, int looping, int32_t position,
     uint32_t position_frac)
 {
-    return StartVoice(c, "oalgpu_voice_init_queue", true, voice, first_buffer, looping, position, position_frac);
+    if(int rc = StartVoice(c, "oalgpu_voice_init_queue", true, voice, first_buffer, looping, position, position_frac)) return rc;
+    if(voice < c->voiceFreq.size()) c->voiceFreq[voice] = 0u;       // (this start names no frequency)
+    return OALGPU_OK;
 }
 
 /* where a streaming voice is: its current buffer (-1: the queue ended) and the number of buffers it has
@@ -250,6 +256,29 @@ int oalgpu_voice_set_hrtf_targets(oalgpu_context *c, const uint32_t *voices, con
     return OALGPU_OK;
 }
 
+// What a parameter block carries besides its records (which are in b->recs): the voice -> record map the voice kernels' in-kernel
+// installs go by, and -- contexts whose voice kernel installs blocks itself -- the records' blended target HRIRs.
+int FinishParamBlock(oalgpu_context *c, oalgpu_param_block *b, const uint32_t *voices, size_t count)
+{
+    std::vector<int32_t> map(c->L.numVoices, -1);
+    bool unique = true;
+    for(size_t i = 0; i < count; ++i) { unique = unique && map[voices[i]] < 0; map[voices[i]] = int32_t(i); }
+    if(!unique) return OALGPU_OK;       // (a block that names a voice twice is applied by ApplyParamsKernel, record by record)
+    HIP_TRY(b->voiceToRec.alloc(map.size()));
+    HIP_TRY(b->voiceToRec.upload(map.data(), map.size()));
+    b->mapVoices = uint32_t(map.size());
+    // (rows of up to 64 taps: InstallPair moves one tap pair per lane; longer responses are blended at install, ApplyRecordLean)
+    if((c->res.enabled || (c->desc.flags & OALGPU_CTX_APPLY_IN_VOICE_KERNEL)) && c->L.hrtf && c->L.hrirs && c->L.irStride <= 64u)
+    {   // a resident context's voice kernel installs the block itself: the HRIR blend of every record now, once
+        HIP_TRY(b->rows.alloc(count * size_t{c->L.irStride} * 2));
+        HIP_TRY(b->rows.zero());
+        LaunchBlendRows(c->stream, c->L, b->recs.p, uint32_t(count), b->rows.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return OALGPU_OK;
+}
+
 int oalgpu_param_block_create(oalgpu_context *c, const uint32_t *voices, const oalgpu_voice_params *params,
     size_t count, oalgpu_param_block **out)
 {
@@ -266,26 +295,7 @@ int oalgpu_param_block_create(oalgpu_context *c, const uint32_t *voices, const o
     b->hrtfGeneration = c->hrtfGeneration;
     HIP_TRY(b->recs.alloc(count));
     HIP_TRY(b->recs.upload(recs.data(), count));
-    {
-        std::vector<int32_t> map(c->L.numVoices, -1);
-        bool unique = true;
-        for(size_t i = 0; i < count; ++i) { unique = unique && map[voices[i]] < 0; map[voices[i]] = int32_t(i); }
-        if(unique)      // (a block that names a voice twice is applied by ApplyParamsKernel, record by record)
-        {
-            HIP_TRY(b->voiceToRec.alloc(map.size()));
-            HIP_TRY(b->voiceToRec.upload(map.data(), map.size()));
-            b->mapVoices = uint32_t(map.size());
-            // (rows of up to 64 taps: InstallPair moves one tap pair per lane; longer responses are blended at install, ApplyRecordLean)
-            if((c->res.enabled || (c->desc.flags & OALGPU_CTX_APPLY_IN_VOICE_KERNEL)) && c->L.hrtf && c->L.hrirs && c->L.irStride <= 64u)
-            {   // a resident context's voice kernel installs the block itself: the HRIR blend of every record now, once
-                HIP_TRY(b->rows.alloc(count * size_t{c->L.irStride} * 2));
-                HIP_TRY(b->rows.zero());
-                LaunchBlendRows(c->stream, c->L, b->recs.p, uint32_t(count), b->rows.p);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipStreamSynchronize(c->stream));
-            }
-        }
-    }
+    if(int rc = FinishParamBlock(c, b.get(), voices, count)) return rc;
     for(size_t i = 0; i < count; ++i)
         if(c->cbOfVoice[voices[i]] >= 0) b->cbSteps.emplace_back(voices[i], params[i].step);
     *out = b.release();

@@ -11,19 +11,6 @@ namespace {
 
 constexpr uint32_t kFracOne = 1u << OALGPU_MIXER_FRAC_BITS;
 
-// float2uint (common/alnumeric.h:223-240): truncating, clamping float -> unsigned.
-uint32_t TruncToUint(float f)
-{
-    int32_t bits;
-    std::memcpy(&bits, &f, sizeof(bits));
-    const uint32_t keep = static_cast<uint32_t>(bits >> 31) ^ 0xffffffffu;
-    const int shift = ((bits >> 23) & 0xff) - (127 + 23);
-    if(shift < -23) return 0;
-    if(shift > 8) return 0xffffffffu & keep;
-    const uint32_t mant = (static_cast<uint32_t>(bits) & 0x7fffffu) | 0x800000u;
-    return ((shift < 0) ? (mant >> -shift) : (mant << shift)) & keep;
-}
-
 int BsincFamily(int resampler)
 {
     switch(resampler)
@@ -53,16 +40,9 @@ void PrepareResampler(int resampler, uint32_t increment, oalgpu_interp_state *ou
     const BsincTable *table = GetBsincTable(family);
 
     // BsincPrepare: scale index + curve-fitted interpolation factor when down-sampling.
-    size_t si = 15;
+    uint32_t si = 15;
     float sf = 0.0f;
-    if(increment > kFracOne)
-    {
-        sf = float(kFracOne) / float(increment) - table->scaleBase;
-        sf = std::max(0.0f, 16.0f * sf * table->scaleRange - 1.0f);
-        si = TruncToUint(sf);
-        sf -= float(si);
-        sf = 1.0f - std::sqrt(1.0f - sf * sf);
-    }
+    if(increment > kFracOne) BsincScale(table->scaleBase, table->scaleRange, increment, si, sf);
     out->kind = (!fastOnly && increment > kFracOne) ? 4 : 3;
     out->table = family;
     out->sf = sf;
@@ -71,67 +51,10 @@ void PrepareResampler(int resampler, uint32_t increment, oalgpu_interp_state *ou
     out->filter_offset = table->filterOffset[si];
 }
 
-void DesignBiquadFromSlope(int type, float f0norm, float gain, float slope, float c[5])
-{
-    gain = std::max(gain, 0.001f);                       // setParamsFromSlope: -60 dB floor
-    DesignBiquad(type, f0norm, gain, std::sqrt((gain + 1.0f / gain) * (1.0f / slope - 1.0f) + 2.0f), c);
-}
-
 void DesignBiquadFromBandwidth(int type, float f0norm, float gain, float bandwidth, float c[5])
 {   // rcpQFromBandwidth, biquad.h:71-75
     const float w0 = 3.14159265358979323846f * 2.0f * f0norm;
     DesignBiquad(type, f0norm, gain, 2.0f * std::sinh(std::log(2.0f) / 2.0f * bandwidth * w0 / std::sin(w0)), c);
-}
-
-void DesignBiquad(int type, float f0norm, float gain, float rcpQ, float c[5])
-{
-    gain = std::max(gain, 0.00001f);                     // SetParams: -100 dB floor
-    const float w0 = 3.14159265358979323846f * 2.0f * std::min(f0norm, 0.49f);
-    const float sw = std::sin(w0), cw = std::cos(w0);
-    const float alpha = sw / 2.0f * rcpQ;
-    float a0 = 1.0f, a1 = 0.0f, a2 = 0.0f, b0 = 1.0f, b1 = 0.0f, b2 = 0.0f;
-    switch(type)
-    {
-    case OALGPU_BIQUAD_HIGHSHELF:
-        {
-            const float sa = 2.0f * std::sqrt(gain) * alpha;
-            b0 = gain * ((gain + 1.0f) + (gain - 1.0f) * cw + sa);
-            b1 = -2.0f * gain * ((gain - 1.0f) + (gain + 1.0f) * cw);
-            b2 = gain * ((gain + 1.0f) + (gain - 1.0f) * cw - sa);
-            a0 = (gain + 1.0f) - (gain - 1.0f) * cw + sa;
-            a1 = 2.0f * ((gain - 1.0f) - (gain + 1.0f) * cw);
-            a2 = (gain + 1.0f) - (gain - 1.0f) * cw - sa;
-        }
-        break;
-    case OALGPU_BIQUAD_LOWSHELF:
-        {
-            const float sa = 2.0f * std::sqrt(gain) * alpha;
-            b0 = gain * ((gain + 1.0f) - (gain - 1.0f) * cw + sa);
-            b1 = 2.0f * gain * ((gain - 1.0f) - (gain + 1.0f) * cw);
-            b2 = gain * ((gain + 1.0f) - (gain - 1.0f) * cw - sa);
-            a0 = (gain + 1.0f) + (gain - 1.0f) * cw + sa;
-            a1 = -2.0f * ((gain - 1.0f) + (gain + 1.0f) * cw);
-            a2 = (gain + 1.0f) + (gain - 1.0f) * cw - sa;
-        }
-        break;
-    case OALGPU_BIQUAD_PEAKING:
-        b0 = 1.0f + alpha * gain; b1 = -2.0f * cw; b2 = 1.0f - alpha * gain;
-        a0 = 1.0f + alpha / gain; a1 = -2.0f * cw; a2 = 1.0f - alpha / gain;
-        break;
-    case OALGPU_BIQUAD_LOWPASS:
-        b0 = (1.0f - cw) / 2.0f; b1 = 1.0f - cw; b2 = (1.0f - cw) / 2.0f;
-        a0 = 1.0f + alpha; a1 = -2.0f * cw; a2 = 1.0f - alpha;
-        break;
-    case OALGPU_BIQUAD_HIGHPASS:
-        b0 = (1.0f + cw) / 2.0f; b1 = -(1.0f + cw); b2 = (1.0f + cw) / 2.0f;
-        a0 = 1.0f + alpha; a1 = -2.0f * cw; a2 = 1.0f - alpha;
-        break;
-    case OALGPU_BIQUAD_BANDPASS:
-        b0 = alpha; b1 = 0.0f; b2 = -alpha;
-        a0 = 1.0f + alpha; a1 = -2.0f * cw; a2 = 1.0f - alpha;
-        break;
-    }
-    c[0] = b0 / a0; c[1] = b1 / a0; c[2] = b2 / a0; c[3] = a1 / a0; c[4] = a2 / a0;
 }
 
 void ApplyBiquadTarget(oalgpu_biquad *f, const float c[5])

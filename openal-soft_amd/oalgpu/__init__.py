@@ -107,6 +107,73 @@ class VoiceParams(C.Structure):
                 ("send_gains", (C.c_float * MAX_AMBI) * MAX_SENDS)]
 
 
+(DISTANCE_DISABLE, DISTANCE_INVERSE, DISTANCE_INVERSE_CLAMPED, DISTANCE_LINEAR, DISTANCE_LINEAR_CLAMPED, DISTANCE_EXPONENT,
+ DISTANCE_EXPONENT_CLAMPED) = range(7)
+
+
+class ListenerParams(C.Structure):
+    """oalgpu_listener_params: ContextParams (core/context.h:67-84) and alu.cpp's file-scope scales; default() = ContextParams{}"""
+    _fields_ = [("matrix", C.c_float * 16), ("position", C.c_float * 3), ("velocity", C.c_float * 3),
+                ("gain", C.c_float), ("meters_per_unit", C.c_float), ("air_absorption_gain_hf", C.c_float),
+                ("doppler_factor", C.c_float), ("speed_of_sound", C.c_float),
+                ("source_distance_model", C.c_int32), ("distance_model", C.c_int32),
+                ("cone_scale", C.c_float), ("nfc_scale", C.c_float), ("xyz_scale", C.c_float * 3)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        p.matrix[:] = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1]
+        p.gain, p.meters_per_unit, p.air_absorption_gain_hf, p.doppler_factor, p.speed_of_sound = 1.0, 1.0, 0.99426, 1.0, 343.3
+        p.source_distance_model, p.distance_model = 0, DISTANCE_DISABLE
+        p.cone_scale, p.nfc_scale = 1.0, 1.0
+        p.xyz_scale[:] = [1.0, 1.0, 1.0]
+        return p
+
+
+class SlotEnvironment(C.Structure):
+    _fields_ = [("active", C.c_int32), ("room_rolloff", C.c_float), ("decay_time", C.c_float), ("air_absorption_gain_hf", C.c_float)]
+
+
+class SourceSend(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("gain", C.c_float), ("gain_hf", C.c_float), ("hf_reference", C.c_float),
+                ("gain_lf", C.c_float), ("lf_reference", C.c_float)]
+
+
+class SourceProps(C.Structure):
+    """oalgpu_source_props: the VoiceProps (core/voice.h:101-158) of a mono 3D point source"""
+    _fields_ = [(n, C.c_float) for n in ("pitch", "gain", "outer_gain", "min_gain", "max_gain", "inner_angle", "outer_angle",
+                                         "ref_distance", "max_distance", "rolloff_factor")] + [
+        ("position", C.c_float * 3), ("velocity", C.c_float * 3), ("direction", C.c_float * 3),
+        ("head_relative", C.c_int32), ("distance_model", C.c_int32), ("resampler", C.c_int32),
+        ("dry_gain_hf_auto", C.c_int32), ("wet_gain_auto", C.c_int32), ("wet_gain_hf_auto", C.c_int32)] + [
+        (n, C.c_float) for n in ("outer_gain_hf", "air_absorption_factor", "room_rolloff_factor", "doppler_factor", "radius",
+                                 "direct_gain", "direct_gain_hf", "direct_hf_reference", "direct_gain_lf", "direct_lf_reference")] + [
+        ("send", SourceSend * MAX_SENDS)]
+
+
+def source_params_host(desc, listener, props_array, frequency, slots=None, dry_map=None, wet_maps=None, mhr=None):
+    """oalgpu_source_params_host: the source stage's arithmetic compiled for the host (no device).  desc: ContextDesc; slots: a
+    ctypes array of SlotEnvironment; dry_map / wet_maps: (index, scale) arrays; mhr: the data set's bytes (HRTF).
+    -> a ctypes array of VoiceParams"""
+    n = len(props_array)
+    out = (VoiceParams * n)()
+    u8p = C.POINTER(C.c_uint8)
+    lib.oalgpu_source_params_host.argtypes = [C.POINTER(ContextDesc), C.POINTER(ListenerParams), C.c_void_p, u8p, f32p, u8p, f32p,
+                                              C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+
+    def maps(m):
+        if m is None:
+            return None, None, None
+        idx = np.ascontiguousarray(m[0], np.uint8); sc = np.ascontiguousarray(m[1], np.float32)
+        return idx.ctypes.data_as(u8p), _fp(sc), (idx, sc)
+    di, ds, keep_d = maps(dry_map)
+    wi, ws, keep_w = maps(wet_maps)
+    check(lib.oalgpu_source_params_host(C.byref(desc), C.byref(listener), C.cast(slots, C.c_void_p) if slots is not None else None,
+                                        di, ds, wi, ws, mhr, len(mhr) if mhr else 0, frequency, C.cast(props_array, C.c_void_p), n,
+                                        C.cast(out, C.c_void_p)), "oalgpu_source_params_host")
+    return out
+
+
 class VoiceState(C.Structure):
     _fields_ = [("play_state", C.c_int32), ("position", C.c_int32), ("position_frac", C.c_uint32),
                 ("has_buffer", C.c_int32), ("fading", C.c_int32),
@@ -583,6 +650,31 @@ class Scene:
         v = np.ascontiguousarray(voices, np.uint32)
         p = np.ascontiguousarray(pans, np.float32).reshape(len(v), 11)
         check(lib.oalgpu_voice_set_pan(self.h, v.ctypes.data_as(u32p), _fp(p), len(v)), "oalgpu_voice_set_pan")
+
+    # 3D source parameters on the GPU: CalcAttnVoiceParams + CalcPanningAndFilters from source properties
+    def set_listener(self, listener):
+        lib.oalgpu_context_set_listener.argtypes = [C.c_void_p, C.POINTER(ListenerParams)]
+        check(lib.oalgpu_context_set_listener(self.h, C.byref(listener)), "oalgpu_context_set_listener")
+
+    def set_slot_send_environment(self, slot, active, room_rolloff=0.0, decay_time=0.0, air_absorption_gain_hf=1.0):
+        lib.oalgpu_slot_set_send_environment.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_float, C.c_float]
+        check(lib.oalgpu_slot_set_send_environment(self.h, slot, 1 if active else 0, room_rolloff, decay_time, air_absorption_gain_hf),
+              "oalgpu_slot_set_send_environment")
+
+    def set_source_props(self, voices, props_array):
+        """voices: uint32 array; props_array: ctypes array of SourceProps"""
+        voices = np.ascontiguousarray(voices, np.uint32)
+        lib.oalgpu_voice_set_source_props.argtypes = [C.c_void_p, u32p, C.c_void_p, C.c_size_t]
+        check(lib.oalgpu_voice_set_source_props(self.h, voices.ctypes.data_as(u32p), C.cast(props_array, C.c_void_p), len(voices)),
+              "oalgpu_voice_set_source_props")
+
+    def param_block_from_sources(self, voices, props_array):
+        voices = np.ascontiguousarray(voices, np.uint32)
+        h = C.c_void_p()
+        lib.oalgpu_param_block_create_from_sources.argtypes = [C.c_void_p, u32p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        check(lib.oalgpu_param_block_create_from_sources(self.h, voices.ctypes.data_as(u32p), C.cast(props_array, C.c_void_p),
+                                                         len(voices), C.byref(h)), "oalgpu_param_block_create_from_sources")
+        return h
 
     # near-field control (same interface as tests/oracle_lib.Scene)
     def set_nfc(self, w1, channels_per_order):
