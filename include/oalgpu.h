@@ -537,6 +537,51 @@ int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_list
     const float *wet_scale, const void *mhr, size_t mhr_size, uint32_t frequency, const oalgpu_source_props *props,
     size_t count, oalgpu_voice_params *out);
 
+/* ---- The same for multi-channel and non-spatialized sources: the rest of CalcVoiceParams -----------------------------
+ * A mono, stereo, rear, quad, 5.1, 6.1 or 7.1 source under any AL_SOURCE_SPATIALIZE_SOFT mode, DirectChannels off.  A
+ * multi-channel source is one voice per channel (oalgpu_buffer_channel_view), in the reference's channel order: stereo L R;
+ * rear BL BR; quad FL FR BL BR; 5.1 FL FR FC LFE SL SR; 6.1 FL FR FC LFE BC SL SR; 7.1 FL FR FC LFE BL BR SL SR.
+ * CalcVoiceParams' route (alc/alu.cpp:2024-2030): spatialize OFF, or AUTO with anything but MONO, takes
+ * CalcNonAttnVoiceParams (:1659-1710: no distance model, cone, absorption or Doppler; the source plays around the listener);
+ * everything else CalcAttnVoiceParams, as above.  Then the multi-channel legs of CalcHrtfPanning (:1229-1310) /
+ * CalcNormalPanning (:1365-1465): every channel's map position (StereoPan for stereo) warped towards the source by the
+ * spread, the left / right balance of `panning` (GetPanGainSelector), a silent LFE channel; the filters, mStep and the
+ * resampler are the source's, equal in all its channel voices.  One kernel (ChannelParamsKernel,
+ * csrc/source_channel_kernels.hip), one wavefront per channel voice.  A MONO source with spatialize ON or AUTO yields what
+ * oalgpu_voice_set_source_props yields for its props (`panning` does not reach a mono source: the reference hands 0 down
+ * unless mPanningEnabled).
+ * NOT covered: DirectChannels other than off (RealOut.ChannelIndex, RemixMap), B-Format / UHJ / Super Stereo sources
+ * (CalcAmbisonicPanning), mPanningEnabled mono sources (MergePannedMono, mDuplicateMono), Pairwise rendering, contexts with
+ * near-field control, callback voices. */
+enum oalgpu_source_channels {           /* FmtChannels, the non-ambisonic ones */
+    OALGPU_CHANNELS_MONO, OALGPU_CHANNELS_STEREO, OALGPU_CHANNELS_REAR, OALGPU_CHANNELS_QUAD,
+    OALGPU_CHANNELS_X51, OALGPU_CHANNELS_X61, OALGPU_CHANNELS_X71 };
+enum oalgpu_spatialize { OALGPU_SPATIALIZE_OFF, OALGPU_SPATIALIZE_ON, OALGPU_SPATIALIZE_AUTO };  /* SpatializeMode, core/voice.h:37-41 */
+#define OALGPU_MAX_SOURCE_CHANNELS 8
+#define OALGPU_NO_VOICE 0xffffffffu     /* this channel has no voice: skipped (an LFE channel nobody mixes) */
+typedef struct oalgpu_channel_source {
+    oalgpu_source_props props;          /* as above */
+    int32_t channels, spatialize;       /* mFmtChannels (oalgpu_source_channels), mSpatializeMode (oalgpu_spatialize) */
+    float stereo_pan[2];                /* StereoPan, radians counter-clockwise (default +pi/6, -pi/6) */
+    float panning;                      /* Panning (balance, -1 .. +1) */
+    uint32_t voices[OALGPU_MAX_SOURCE_CHANNELS];   /* the channel voices, in the reference's channel order */
+} oalgpu_channel_source;
+/* The synchronous form: sources[i].voices[c] <- channel c of source i, for the channels of its layout; entries past the
+ * layout's channel count are not read.  Refuses, with nothing changed, what oalgpu_voice_set_source_props refuses, and with
+ * OALGPU_ERR_INVALID: channels or spatialize out of range; a voice named twice in one call; channel voices of one source
+ * with different frequencies or without one; a source whose channel voices are all OALGPU_NO_VOICE. */
+int oalgpu_voice_set_channel_sources(oalgpu_context *ctx, const oalgpu_channel_source *sources, size_t count);
+/* The same into an ordinary oalgpu_param_block, as oalgpu_param_block_create_from_sources. */
+int oalgpu_param_block_create_from_channel_sources(oalgpu_context *ctx, const oalgpu_channel_source *sources, size_t count,
+    oalgpu_param_block **out);
+/* The same arithmetic compiled for the host, with oalgpu_source_params_host's arguments: out[i * OALGPU_MAX_SOURCE_CHANNELS
+ * + c] <- channel c of sources[i]; the records of channels the layout does not have are zeroed, sources[i].voices is not
+ * read.  An LFE channel's record carries the source's step and filters and no gain. */
+int oalgpu_channel_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
+    const oalgpu_slot_environment *slots, const uint8_t *dry_index, const float *dry_scale, const uint8_t *wet_index,
+    const float *wet_scale, const void *mhr, size_t mhr_size, uint32_t frequency, const oalgpu_channel_source *sources,
+    size_t count, oalgpu_voice_params *out);
+
 /* One update: zero the dry/real and wet buses, mix every Playing|Stopping voice
  * (Voice::mix, core/voice.cpp:988-1233), and -- HRTF context, post_process != 0 -- run
  * MixDirectHrtf over the dry bus (DeviceBase::Process(HrtfPostProcess), alc/alu.cpp:289-298).

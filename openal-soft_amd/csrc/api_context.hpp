@@ -39,7 +39,7 @@
 #include "../host/tables.hpp"
 #include "api_util.hpp"
 #include "kernels.hpp"
-#include "dev_source.hpp"
+#include "dev_source_channels.hpp"
 #include "bus_merge.hpp"
 #include "reverb_dev.hpp"
 
@@ -285,6 +285,8 @@ struct oalgpu_context {
     DevBuf<SourceRecord> srcDev;
     std::vector<SourceRecord> srcHost;
     std::vector<uint32_t> srcVoices;        // (the voices of srcHost: a voice named twice keeps its last record)
+    DevBuf<ChannelSourceRecord> chanDev;    // channel sources (oalgpu_voice_set_channel_sources): their staging; srcVoices: the
+    std::vector<ChannelSourceRecord> chanHost;      // channel voices in the order of their records
     // callback sources (oalgpu_voice_init_callback): the host's mirror of what Voice::mix keeps for them
     struct CbVoice {
         uint32_t voice{0}; int32_t buffer{-1}; uint32_t frameBytes{4}, capacityFrames{0};

@@ -1,6 +1,7 @@
 // 3D source parameters computed on the GPU: the listener, the slots' send environments, and the entry points that turn source
 // properties into parameter records with SourceParamsKernel (source_kernels.hip) -- and the same arithmetic (dev_source.hpp)
-// compiled for the host, oalgpu_source_params_host.
+// compiled for the host, oalgpu_source_params_host.  The same for multi-channel and non-spatialized sources: channel sources,
+// ChannelParamsKernel (source_channel_kernels.hip), dev_source_channels.hpp, oalgpu_channel_source_params_host.
 #include "api_context.hpp"
 
 namespace {
@@ -88,6 +89,129 @@ int CollectSources(oalgpu_context *c, const char *who, const uint32_t *voices, c
     return OALGPU_OK;
 }
 
+// the same for channel sources: the records (c->chanHost, with their places in the output) and the voices in output order
+// (c->srcVoices)
+int CollectChannelSources(oalgpu_context *c, const char *who, const oalgpu_channel_source *sources, size_t count)
+{
+    const std::string name(who);
+    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, name + ": HRTF context without a data set");
+    if(c->L.nfc)
+        return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control (the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
+    std::vector<uint8_t> named(c->L.numVoices, 0);
+    c->chanHost.clear(); c->srcVoices.clear();
+    for(size_t i = 0; i < count; ++i)
+    {
+        const oalgpu_channel_source &src = sources[i];
+        if(src.channels < OALGPU_CHANNELS_MONO || src.channels > OALGPU_CHANNELS_X71 || src.spatialize < OALGPU_SPATIALIZE_OFF
+            || src.spatialize > OALGPU_SPATIALIZE_AUTO)
+            return Fail(OALGPU_ERR_INVALID, name + ": channels or spatialize out of range");
+        if(!PropsOk(src.props, c->L.numSends, c->L.numSlots))
+            return Fail(OALGPU_ERR_INVALID, name + ": resampler, distance model or send slot out of range");
+        ChannelSourceRecord rec{};
+        rec.outBase = uint32_t(c->srcVoices.size());
+        rec.channels = src.channels; rec.spatialize = src.spatialize;
+        rec.stereoPan[0] = src.stereo_pan[0]; rec.stereoPan[1] = src.stereo_pan[1]; rec.panning = src.panning;
+        rec.p = src.props;
+        for(uint32_t ch = 0; ch < OALGPU_MAX_SOURCE_CHANNELS; ++ch) rec.voices[ch] = OALGPU_NO_VOICE;
+        for(uint32_t ch = 0; ch < SourceChannelCount(src.channels); ++ch)
+        {
+            const uint32_t v = src.voices[ch];
+            if(v == OALGPU_NO_VOICE) continue;
+            if(v >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, name + ": bad voice index");
+            if(c->cbOfVoice[v] >= 0)
+                return Fail(OALGPU_ERR_INVALID, name + ": not for callback voices (their step is mirrored on the host: oalgpu_voice_set_params)");
+            if(named[v]) return Fail(OALGPU_ERR_INVALID, name + ": a voice named twice");
+            named[v] = 1;
+            const uint32_t freq = v < c->voiceFreq.size() ? c->voiceFreq[v] : 0u;
+            if(freq == 0u) return Fail(OALGPU_ERR_INVALID, name + ": the voice has no frequency (start it with oalgpu_voice_init)");
+            if(rec.frequency && rec.frequency != freq)
+                return Fail(OALGPU_ERR_INVALID, name + ": the channel voices of a source have different frequencies");
+            rec.frequency = freq;
+            rec.voices[ch] = v;
+            rec.present |= 1u << ch;
+            c->srcVoices.push_back(v);
+        }
+        if(!rec.frequency) return Fail(OALGPU_ERR_INVALID, name + ": a source without a channel voice");
+        c->chanHost.push_back(rec);
+    }
+    return OALGPU_OK;
+}
+
+// a context as oalgpu_source_params_host and oalgpu_channel_source_params_host are told of it: the stage's set-up over host memory
+struct HostStage {
+    std::vector<oalgpu_slot_environment> env;
+    std::vector<AmbiMapEntry> dryMap, wetMaps;
+    HrtfData hrtf;
+    HrtfStoreDev store{};
+    SourceSetup cx{};
+
+    int build(const char *who, const oalgpu_context_desc *desc, const oalgpu_listener_params *listener, const oalgpu_slot_environment *slots,
+        const uint8_t *dry_index, const float *dry_scale, const uint8_t *wet_index, const float *wet_scale, const void *mhr,
+        size_t mhr_size, uint32_t frequency, bool arraysOk)
+    {
+        const std::string name(who);
+        if(!desc || !listener || !arraysOk || frequency == 0u || desc->sample_rate == 0u)
+            return Fail(OALGPU_ERR_INVALID, name + ": bad arguments");
+        if(desc->num_aux_sends > OALGPU_MAX_SENDS || desc->num_dry_channels > OALGPU_MAX_OUTPUT_CHANNELS
+            || desc->wet_channels > OALGPU_MAX_AMBI_CHANNELS || !dry_index != !dry_scale || !wet_index != !wet_scale)
+            return Fail(OALGPU_ERR_INVALID, name + ": bad arguments");
+        const uint32_t numDry = desc->num_dry_channels, numSlots = desc->num_slots, wet = desc->wet_channels;
+        env.assign(numSlots, oalgpu_slot_environment{0, 0.0f, 0.0f, 1.0f});
+        if(slots) std::copy(slots, slots + numSlots, env.begin());
+        dryMap.resize(numDry); wetMaps.resize(size_t{numSlots} * wet);
+        for(uint32_t i = 0; i < numDry; ++i) dryMap[i] = dry_index ? AmbiMapEntry{dry_index[i], dry_scale[i]} : AmbiMapEntry{i, 1.0f};
+        for(size_t i = 0; i < wetMaps.size(); ++i)
+            wetMaps[i] = wet_index ? AmbiMapEntry{wet_index[i], wet_scale[i]} : AmbiMapEntry{uint32_t(i % wet), 1.0f};
+        for(const AmbiMapEntry &m : dryMap) if(m.index >= OALGPU_MAX_AMBI_CHANNELS) return Fail(OALGPU_ERR_INVALID, "ambisonic channel index out of range");
+        for(const AmbiMapEntry &m : wetMaps) if(m.index >= OALGPU_MAX_AMBI_CHANNELS) return Fail(OALGPU_ERR_INVALID, "ambisonic channel index out of range");
+        if(desc->hrtf)
+        {
+            if(!mhr) return Fail(OALGPU_ERR_NO_HRTF, name + ": HRTF context without a data set");
+            const std::string err = ParseMhr(mhr, mhr_size, hrtf);
+            if(!err.empty()) return Fail(OALGPU_ERR_INVALID, "mhr: " + err);
+            ResampleHrtfData(hrtf, desc->sample_rate);
+            store = HostStoreView(hrtf);
+        }
+        cx = SourceSetup{desc->sample_rate, desc->num_aux_sends, numSlots, numDry, wet, desc->hrtf ? 1u : 0u, env.data(),
+            &HostResamplerConsts(), dryMap.data(), wetMaps.data()};
+        return OALGPU_OK;
+    }
+};
+
+// what the stage leaves for one channel voice, as an oalgpu_voice_params: the filters' parameters in place of the designs,
+// the resolved line gains
+void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const SourceGains &g, const ChannelPan &pan, const HostStage &h)
+{
+    const SourceSetup &cx = h.cx;
+    std::memset(&o, 0, sizeof(o));
+    const uint32_t flags = SourceFilterFlags(g, cx.numSends);
+    o.step = g.step;
+    o.resampler = p.resampler;
+    const float invSampleRate = 1.0f / float(cx.sampleRate);
+    o.direct_filter = oalgpu_filter_params{(flags & kFlagDirectFilter) ? 1 : 0, g.dryHF, p.direct_hf_reference * invSampleRate,
+        g.dryLF, p.direct_lf_reference * invSampleRate};
+    o.hrtf_ev = pan.hrtfEv; o.hrtf_az = pan.hrtfAz; o.hrtf_dist = pan.hrtfDist; o.hrtf_spread = pan.hrtfSpread;
+    const float dryGain = g.dryBase * pan.pangain;
+    o.hrtf_gain = dryGain;
+    const float ay = -pan.dir[0], az = pan.dir[1], ax = -pan.dir[2];
+    if(!cx.hrtf && !pan.silent)
+        for(uint32_t t = 0; t < cx.numDry; ++t)
+            o.dry_gains[t] = PanLineGain(h.dryMap[t].index, h.dryMap[t].scale, ay, az, ax, pan.drySpread, dryGain);
+    for(uint32_t s = 0; s < OALGPU_MAX_SENDS; ++s)
+    {
+        o.send_slot[s] = g.sendSlot[s];
+        if(s >= cx.numSends) continue;
+        o.send_filter[s] = oalgpu_filter_params{(flags >> (kFlagSendFilterShift + s)) & 1u ? 1 : 0, g.wetHF[s],
+            p.send[s].hf_reference * invSampleRate, g.wetLF[s], p.send[s].lf_reference * invSampleRate};
+        if(g.sendSlot[s] < 0 || pan.silent) continue;
+        for(uint32_t ch = 0; ch < cx.wetChannels; ++ch)
+        {
+            const AmbiMapEntry &m = h.wetMaps[size_t(g.sendSlot[s]) * cx.wetChannels + ch];
+            o.send_gains[s][ch] = PanLineGain(m.index, m.scale, ay, az, ax, pan.sendSpread, g.wetBase[s] * pan.pangain);
+        }
+    }
+}
+
 } // namespace
 
 int oalgpu_context_set_listener(oalgpu_context *c, const oalgpu_listener_params *listener)
@@ -158,64 +282,99 @@ int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_list
     const float *wet_scale, const void *mhr, size_t mhr_size, uint32_t frequency, const oalgpu_source_props *props, size_t count,
     oalgpu_voice_params *out)
 {
-    if(!desc || !listener || !props || !out || frequency == 0u || desc->sample_rate == 0u)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_source_params_host: bad arguments");
-    if(desc->num_aux_sends > OALGPU_MAX_SENDS || desc->num_dry_channels > OALGPU_MAX_OUTPUT_CHANNELS
-        || desc->wet_channels > OALGPU_MAX_AMBI_CHANNELS || !dry_index != !dry_scale || !wet_index != !wet_scale)
-        return Fail(OALGPU_ERR_INVALID, "oalgpu_source_params_host: bad arguments");
-    const uint32_t numDry = desc->num_dry_channels, numSlots = desc->num_slots, wet = desc->wet_channels;
-    std::vector<oalgpu_slot_environment> env(numSlots, oalgpu_slot_environment{0, 0.0f, 0.0f, 1.0f});
-    if(slots) std::copy(slots, slots + numSlots, env.begin());
-    std::vector<AmbiMapEntry> dryMap(numDry), wetMaps(size_t{numSlots} * wet);
-    for(uint32_t i = 0; i < numDry; ++i) dryMap[i] = dry_index ? AmbiMapEntry{dry_index[i], dry_scale[i]} : AmbiMapEntry{i, 1.0f};
-    for(size_t i = 0; i < wetMaps.size(); ++i)
-        wetMaps[i] = wet_index ? AmbiMapEntry{wet_index[i], wet_scale[i]} : AmbiMapEntry{uint32_t(i % wet), 1.0f};
-    for(const AmbiMapEntry &m : dryMap) if(m.index >= OALGPU_MAX_AMBI_CHANNELS) return Fail(OALGPU_ERR_INVALID, "ambisonic channel index out of range");
-    for(const AmbiMapEntry &m : wetMaps) if(m.index >= OALGPU_MAX_AMBI_CHANNELS) return Fail(OALGPU_ERR_INVALID, "ambisonic channel index out of range");
-    HrtfData hrtf;
-    HrtfStoreDev store{};
-    if(desc->hrtf)
-    {
-        if(!mhr) return Fail(OALGPU_ERR_NO_HRTF, "oalgpu_source_params_host: HRTF context without a data set");
-        const std::string err = ParseMhr(mhr, mhr_size, hrtf);
-        if(!err.empty()) return Fail(OALGPU_ERR_INVALID, "mhr: " + err);
-        ResampleHrtfData(hrtf, desc->sample_rate);
-        store = HostStoreView(hrtf);
-    }
-    const ResamplerConsts &rs = HostResamplerConsts();
-    const SourceSetup cx{desc->sample_rate, desc->num_aux_sends, numSlots, numDry, wet, desc->hrtf ? 1u : 0u, env.data(), &rs,
-        dryMap.data(), wetMaps.data()};
+    HostStage h;
+    if(int rc = h.build("oalgpu_source_params_host", desc, listener, slots, dry_index, dry_scale, wet_index, wet_scale, mhr, mhr_size,
+        frequency, props && out))
+        return rc;
+    const float frontPan[2] = {0.0f, 0.0f};
     for(size_t i = 0; i < count; ++i)
     {
         const oalgpu_source_props &p = props[i];
-        if(!PropsOk(p, cx.numSends, numSlots)) return Fail(OALGPU_ERR_INVALID, "oalgpu_source_params_host: resampler, distance model or send slot out of range");
-        oalgpu_voice_params &o = out[i];
-        std::memset(&o, 0, sizeof(o));
-        const SourceGains g = SourceAttenuation(p, frequency, *listener, cx);
-        const uint32_t flags = SourceFilterFlags(g, cx.numSends);
-        o.step = g.step;
-        o.resampler = p.resampler;
-        const float invSampleRate = 1.0f / float(cx.sampleRate);
-        o.direct_filter = oalgpu_filter_params{(flags & kFlagDirectFilter) ? 1 : 0, g.dryHF, p.direct_hf_reference * invSampleRate,
-            g.dryLF, p.direct_lf_reference * invSampleRate};
-        o.hrtf_ev = g.hrtfEv; o.hrtf_az = g.hrtfAz; o.hrtf_dist = g.hrtfDist; o.hrtf_spread = g.spread;
-        o.hrtf_gain = g.dryBase;
-        const float ay = -g.dir[0], az = g.dir[1], ax = -g.dir[2];
-        if(!cx.hrtf)
-            for(uint32_t t = 0; t < numDry; ++t)
-                o.dry_gains[t] = PanLineGain(dryMap[t].index, dryMap[t].scale, ay, az, ax, g.spread, g.dryBase);
-        for(uint32_t s = 0; s < OALGPU_MAX_SENDS; ++s)
+        if(!PropsOk(p, h.cx.numSends, h.cx.numSlots)) return Fail(OALGPU_ERR_INVALID, "oalgpu_source_params_host: resampler, distance model or send slot out of range");
+        const SourceGains g = SourceAttenuation(p, frequency, *listener, h.cx);
+        FillVoiceParams(out[i], p, g, ChannelPanning(ChannelSeatOf(OALGPU_CHANNELS_MONO, 0u, frontPan, 0.0f), g, h.cx.hrtf), h);
+    }
+    return OALGPU_OK;
+}
+
+// the channel sources of c->chanHost -> their records at `out`
+static int RunChannelStage(oalgpu_context *c, ParamRecord *out)
+{
+    if(int rc = StageRecords(c->stream, c->chanDev, c->chanHost.data(), c->chanHost.size())) return rc;
+    uint32_t maxChannels = 1;
+    for(const ChannelSourceRecord &r : c->chanHost) maxChannels = std::max(maxChannels, SourceChannelCount(r.channels));
+    LaunchChannelParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->chanDev.p, uint32_t(c->chanHost.size()), maxChannels, out);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+int oalgpu_voice_set_channel_sources(oalgpu_context *c, const oalgpu_channel_source *sources, size_t count)
+{
+    if(!c || !sources) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_channel_sources: null argument");
+    if(count == 0) return OALGPU_OK;
+    if(int rc = CollectChannelSources(c, "oalgpu_voice_set_channel_sources", sources, count)) return rc;
+    if(int rc = BeginVoiceCall(c)) return rc;
+    if(int rc = EnsureSourceStage(c)) return rc;
+    const size_t records = c->srcVoices.size();
+    if(c->paramDev.n < records) HIP_TRY(c->paramDev.alloc(records));
+    if(int rc = RunChannelStage(c, c->paramDev.p)) return rc;
+    LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(records));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OALGPU_OK;
+}
+
+int oalgpu_param_block_create_from_channel_sources(oalgpu_context *c, const oalgpu_channel_source *sources, size_t count,
+    oalgpu_param_block **out)
+{
+    if(!c || !sources || !out || count == 0)
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_param_block_create_from_channel_sources: bad arguments");
+    *out = nullptr;
+    if(int rc = CollectChannelSources(c, "oalgpu_param_block_create_from_channel_sources", sources, count)) return rc;
+    if(int rc = UseCtx(c)) return rc;
+    if(int rc = EnsureSourceStage(c)) return rc;
+    const size_t records = c->srcVoices.size();
+    auto b = std::make_unique<oalgpu_param_block>();
+    b->count = uint32_t(records);
+    b->device = c->desc.device;
+    b->hrtfGeneration = c->hrtfGeneration;
+    HIP_TRY(b->recs.alloc(records));
+    if(int rc = RunChannelStage(c, b->recs.p)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
+    if(int rc = FinishParamBlock(c, b.get(), c->srcVoices.data(), records)) return rc;
+    *out = b.release();
+    return OALGPU_OK;
+}
+
+int oalgpu_channel_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
+    const oalgpu_slot_environment *slots, const uint8_t *dry_index, const float *dry_scale, const uint8_t *wet_index,
+    const float *wet_scale, const void *mhr, size_t mhr_size, uint32_t frequency, const oalgpu_channel_source *sources, size_t count,
+    oalgpu_voice_params *out)
+{
+    HostStage h;
+    if(int rc = h.build("oalgpu_channel_source_params_host", desc, listener, slots, dry_index, dry_scale, wet_index, wet_scale, mhr,
+        mhr_size, frequency, sources && out))
+        return rc;
+    for(size_t i = 0; i < count; ++i)
+    {
+        const oalgpu_channel_source &src = sources[i];
+        if(src.channels < OALGPU_CHANNELS_MONO || src.channels > OALGPU_CHANNELS_X71 || src.spatialize < OALGPU_SPATIALIZE_OFF
+            || src.spatialize > OALGPU_SPATIALIZE_AUTO)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_params_host: channels or spatialize out of range");
+        if(!PropsOk(src.props, h.cx.numSends, h.cx.numSlots))
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_params_host: resampler, distance model or send slot out of range");
+    }
+    for(size_t i = 0; i < count; ++i)
+    {
+        const oalgpu_channel_source &src = sources[i];
+        const SourceGains g = SourceRoute(src.channels, src.spatialize) ? SourceAttenuation(src.props, frequency, *listener, h.cx)
+            : SourceNonAttenuation(src.props, frequency, *listener, h.cx);
+        const float stereoPan[2] = {src.stereo_pan[0], src.stereo_pan[1]};
+        for(uint32_t ch = 0; ch < OALGPU_MAX_SOURCE_CHANNELS; ++ch)
         {
-            o.send_slot[s] = g.sendSlot[s];
-            if(s >= cx.numSends) continue;
-            o.send_filter[s] = oalgpu_filter_params{(flags >> (kFlagSendFilterShift + s)) & 1u ? 1 : 0, g.wetHF[s],
-                p.send[s].hf_reference * invSampleRate, g.wetLF[s], p.send[s].lf_reference * invSampleRate};
-            if(g.sendSlot[s] < 0) continue;
-            for(uint32_t ch = 0; ch < wet; ++ch)
-            {
-                const AmbiMapEntry &m = wetMaps[size_t(g.sendSlot[s]) * wet + ch];
-                o.send_gains[s][ch] = PanLineGain(m.index, m.scale, ay, az, ax, g.spread, g.wetBase[s]);
-            }
+            oalgpu_voice_params &o = out[i * OALGPU_MAX_SOURCE_CHANNELS + ch];
+            if(ch >= SourceChannelCount(src.channels)) std::memset(&o, 0, sizeof(o));
+            else FillVoiceParams(o, src.props, g, ChannelPanning(ChannelSeatOf(src.channels, ch, stereoPan, src.panning), g, h.cx.hrtf), h);
         }
     }
     return OALGPU_OK;

@@ -151,15 +151,15 @@ class SourceProps(C.Structure):
         ("send", SourceSend * MAX_SENDS)]
 
 
-def source_params_host(desc, listener, props_array, frequency, slots=None, dry_map=None, wet_maps=None, mhr=None):
-    """oalgpu_source_params_host: the source stage's arithmetic compiled for the host (no device).  desc: ContextDesc; slots: a
-    ctypes array of SlotEnvironment; dry_map / wet_maps: (index, scale) arrays; mhr: the data set's bytes (HRTF).
-    -> a ctypes array of VoiceParams"""
-    n = len(props_array)
-    out = (VoiceParams * n)()
+def _params_host(name, per_source, desc, listener, sources, frequency, slots, dry_map, wet_maps, mhr):
+    """the two host forms of the source stage share their arguments: `name`(desc, listener, slots, the maps, mhr, frequency, sources,
+    count, out) -> a ctypes array of per_source VoiceParams per source"""
+    n = len(sources)
+    out = (VoiceParams * (n * per_source))()
     u8p = C.POINTER(C.c_uint8)
-    lib.oalgpu_source_params_host.argtypes = [C.POINTER(ContextDesc), C.POINTER(ListenerParams), C.c_void_p, u8p, f32p, u8p, f32p,
-                                              C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+    fn = getattr(lib, name)
+    fn.argtypes = [C.POINTER(ContextDesc), C.POINTER(ListenerParams), C.c_void_p, u8p, f32p, u8p, f32p,
+                   C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
 
     def maps(m):
         if m is None:
@@ -168,10 +168,44 @@ def source_params_host(desc, listener, props_array, frequency, slots=None, dry_m
         return idx.ctypes.data_as(u8p), _fp(sc), (idx, sc)
     di, ds, keep_d = maps(dry_map)
     wi, ws, keep_w = maps(wet_maps)
-    check(lib.oalgpu_source_params_host(C.byref(desc), C.byref(listener), C.cast(slots, C.c_void_p) if slots is not None else None,
-                                        di, ds, wi, ws, mhr, len(mhr) if mhr else 0, frequency, C.cast(props_array, C.c_void_p), n,
-                                        C.cast(out, C.c_void_p)), "oalgpu_source_params_host")
+    check(fn(C.byref(desc), C.byref(listener), C.cast(slots, C.c_void_p) if slots is not None else None,
+             di, ds, wi, ws, mhr, len(mhr) if mhr else 0, frequency, C.cast(sources, C.c_void_p), n, C.cast(out, C.c_void_p)), name)
     return out
+
+
+def source_params_host(desc, listener, props_array, frequency, slots=None, dry_map=None, wet_maps=None, mhr=None):
+    """oalgpu_source_params_host: the source stage's arithmetic compiled for the host (no device).  desc: ContextDesc; slots: a
+    ctypes array of SlotEnvironment; dry_map / wet_maps: (index, scale) arrays; mhr: the data set's bytes (HRTF).
+    -> a ctypes array of VoiceParams"""
+    return _params_host("oalgpu_source_params_host", 1, desc, listener, props_array, frequency, slots, dry_map, wet_maps, mhr)
+
+
+(CHANNELS_MONO, CHANNELS_STEREO, CHANNELS_REAR, CHANNELS_QUAD, CHANNELS_X51, CHANNELS_X61, CHANNELS_X71) = range(7)
+SOURCE_CHANNEL_COUNT = (1, 2, 2, 4, 6, 7, 8)        # the channel voices of a layout, in the reference's channel order
+SPATIALIZE_OFF, SPATIALIZE_ON, SPATIALIZE_AUTO = range(3)
+MAX_SOURCE_CHANNELS = 8
+NO_VOICE = 0xffffffff
+
+
+class ChannelSource(C.Structure):
+    """oalgpu_channel_source: a mono .. 7.1 source under any spatialize mode, one voice per channel"""
+    _fields_ = [("props", SourceProps), ("channels", C.c_int32), ("spatialize", C.c_int32), ("stereo_pan", C.c_float * 2),
+                ("panning", C.c_float), ("voices", C.c_uint32 * MAX_SOURCE_CHANNELS)]
+
+    @classmethod
+    def make(cls, props, channels, spatialize=SPATIALIZE_AUTO, voices=(), stereo_pan=(np.pi / 6.0, -np.pi / 6.0), panning=0.0):
+        s = cls()
+        s.props, s.channels, s.spatialize, s.panning = props, channels, spatialize, panning
+        s.stereo_pan[:] = stereo_pan
+        s.voices[:] = (list(voices) + [NO_VOICE] * MAX_SOURCE_CHANNELS)[:MAX_SOURCE_CHANNELS]
+        return s
+
+
+def channel_source_params_host(desc, listener, sources_array, frequency, slots=None, dry_map=None, wet_maps=None, mhr=None):
+    """oalgpu_channel_source_params_host: source_params_host for a ctypes array of ChannelSource
+    -> a ctypes array of VoiceParams, MAX_SOURCE_CHANNELS per source (the channels a layout does not have zeroed)"""
+    return _params_host("oalgpu_channel_source_params_host", MAX_SOURCE_CHANNELS, desc, listener, sources_array, frequency, slots,
+                        dry_map, wet_maps, mhr)
 
 
 class VoiceState(C.Structure):
@@ -674,6 +708,20 @@ class Scene:
         lib.oalgpu_param_block_create_from_sources.argtypes = [C.c_void_p, u32p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         check(lib.oalgpu_param_block_create_from_sources(self.h, voices.ctypes.data_as(u32p), C.cast(props_array, C.c_void_p),
                                                          len(voices), C.byref(h)), "oalgpu_param_block_create_from_sources")
+        return h
+
+    # the same for multi-channel and non-spatialized sources: one voice per channel (add_ambi_voice starts them)
+    def set_channel_sources(self, sources_array):
+        """sources_array: ctypes array of ChannelSource"""
+        lib.oalgpu_voice_set_channel_sources.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        check(lib.oalgpu_voice_set_channel_sources(self.h, C.cast(sources_array, C.c_void_p), len(sources_array)),
+              "oalgpu_voice_set_channel_sources")
+
+    def param_block_from_channel_sources(self, sources_array):
+        h = C.c_void_p()
+        lib.oalgpu_param_block_create_from_channel_sources.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        check(lib.oalgpu_param_block_create_from_channel_sources(self.h, C.cast(sources_array, C.c_void_p), len(sources_array),
+                                                                 C.byref(h)), "oalgpu_param_block_create_from_channel_sources")
         return h
 
     # near-field control (same interface as tests/oracle_lib.Scene)
