@@ -324,6 +324,13 @@ int oalgpu_voice_init(oalgpu_context *ctx, uint32_t voice, const oalgpu_voice_de
  * from that order's NFC-filtered copy. */
 int oalgpu_context_set_nfc(oalgpu_context *ctx, float w1, const uint32_t channels_per_order[5]);
 int oalgpu_voice_set_nfc(oalgpu_context *ctx, uint32_t voice, float w0);
+/* DeviceBase::AvgSpeakerDist, the value the voice side of the reference reads (alc/alu.cpp:1328-1341, :1415-1428): with it a
+ * near-field context computes every source's w0 and NFCtrlFilter.adjust itself, from source properties (the source entry
+ * points below: SourceNfcKernel, csrc/source_nfc_kernels.hip).  Valid after oalgpu_context_set_nfc, with a finite distance
+ * > 0; may be called again; waits for the context's work in flight.  It does NOT touch the control filter's w1: the caller
+ * keeps the two consistent, as InitNearFieldCtrl does (alc/panning.cpp:285-299): w1 = 343.3f / avg_speaker_dist / sample_rate,
+ * in that order of operations. */
+int oalgpu_context_set_nfc_distance(oalgpu_context *ctx, float avg_speaker_dist);
 
 /* VoiceFlag::IsAmbisonic for this (channel) voice: ChannelData::mAmbiSplitter.init(xover_norm),
  * mAmbiHFScale, mAmbiLFScale as Voice::prepare sets them up for a B-Format source on a
@@ -517,12 +524,18 @@ typedef struct oalgpu_source_props {
  * listener and the slot environments as they are now; the voice's frequency is the one of its oalgpu_voice_desc.  Of two
  * records of one voice the last wins.  OALGPU_ERR_INVALID, with nothing changed: a null argument, a voice index, a
  * resampler, a distance model or a send slot out of range; a callback voice (its mStep is mirrored on the host); a context
- * with near-field control (oalgpu_context_set_nfc: the per-voice w0 adjust stays host-side).  OALGPU_ERR_NO_HRTF: an HRTF
- * context without a data set. */
+ * with near-field control (oalgpu_context_set_nfc) that has not been told its speaker distance
+ * (oalgpu_context_set_nfc_distance: until then the per-voice w0 adjust stays host-side, oalgpu_voice_set_nfc).
+ * OALGPU_ERR_NO_HRTF: an HRTF context without a data set.
+ * On a near-field context that knows its speaker distance the call also does what CalcNormalPanning does there: w0 =
+ * 343.3 / (max(distance * NfcScale, AvgSpeakerDist / 4) * rate) for a source away from the listener, the "identity" w0 =
+ * 343.3 / (AvgSpeakerDist * rate) for one at the listener or on CalcNonAttnVoiceParams' route, NFCtrlFilter.adjust(w0) and
+ * VoiceFlag::HasNfc in every channel voice of the source (the LFE channel's too); the filters' histories are kept. */
 int oalgpu_voice_set_source_props(oalgpu_context *ctx, const uint32_t *voices, const oalgpu_source_props *props, size_t count);
 /* The same into an ordinary oalgpu_param_block (oalgpu_param_block_apply, oalgpu_mix_update_run), with the listener and the
  * slot environments as they are at creation time; of two records of one voice the block keeps the last.  Refuses what
- * oalgpu_voice_set_source_props refuses. */
+ * oalgpu_voice_set_source_props refuses.  On a near-field context the block carries the voices' NfcFilter adjusts beside its
+ * records, and oalgpu_param_block_apply / oalgpu_mix_update_run install them with the records. */
 int oalgpu_param_block_create_from_sources(oalgpu_context *ctx, const uint32_t *voices, const oalgpu_source_props *props,
     size_t count, oalgpu_param_block **out);
 /* The same arithmetic compiled for the host (glibc's libm; no device needed): out[i] <- props[i] for a context of `desc`
@@ -551,8 +564,8 @@ int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_list
  * oalgpu_voice_set_source_props yields for its props (`panning` does not reach a mono source: the reference hands 0 down
  * unless mPanningEnabled).
  * NOT covered: DirectChannels other than off (RealOut.ChannelIndex, RemixMap), B-Format / UHJ / Super Stereo sources
- * (CalcAmbisonicPanning), mPanningEnabled mono sources (MergePannedMono, mDuplicateMono), Pairwise rendering, contexts with
- * near-field control, callback voices. */
+ * (CalcAmbisonicPanning: on a near-field context they keep oalgpu_voice_set_nfc), mPanningEnabled mono sources
+ * (MergePannedMono, mDuplicateMono), Pairwise rendering, callback voices. */
 enum oalgpu_source_channels {           /* FmtChannels, the non-ambisonic ones */
     OALGPU_CHANNELS_MONO, OALGPU_CHANNELS_STEREO, OALGPU_CHANNELS_REAR, OALGPU_CHANNELS_QUAD,
     OALGPU_CHANNELS_X51, OALGPU_CHANNELS_X61, OALGPU_CHANNELS_X71 };
@@ -581,6 +594,21 @@ int oalgpu_channel_source_params_host(const oalgpu_context_desc *desc, const oal
     const oalgpu_slot_environment *slots, const uint8_t *dry_index, const float *dry_scale, const uint8_t *wet_index,
     const float *wet_scale, const void *mhr, size_t mhr_size, uint32_t frequency, const oalgpu_channel_source *sources,
     size_t count, oalgpu_voice_params *out);
+/* The near-field side of the same stage compiled for the host: for sources[i] (a mono source is a channel source with
+ * OALGPU_CHANNELS_MONO; sources[i].voices is not read) on a non-HRTF context of `desc` whose speakers are avg_speaker_dist
+ * away, w0[i] <- the w0 the reference hands to NFCtrlFilter.adjust, and coeffs[i * 14 ...] <- what adjust leaves in every
+ * channel voice of the source: a[o][0] for the orders o = 1..4, then b[1][1], b[2][1..2], b[3][1..3], b[4][1..4], of a
+ * control filter designed as InitNearFieldCtrl does from w1 = 343.3f / avg_speaker_dist / desc->sample_rate.  slots, frequency:
+ * as oalgpu_source_params_host.  Bit for bit what SourceNfcKernel computes. */
+int oalgpu_channel_source_nfc_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
+    const oalgpu_slot_environment *slots, float avg_speaker_dist, uint32_t frequency, const oalgpu_channel_source *sources,
+    size_t count, float *w0, float *coeffs);
+/* Host only.  What oalgpu_voice_set_nfc(voice, w0) designs for a voice of a context set up with oalgpu_context_set_nfc(w1):
+ * NfcFilter::init(w1), adjust(w0); coeffs[14] in the order above. */
+int oalgpu_nfc_adjust_host(float w1, float w0, float *coeffs);
+/* What NFCtrlFilter.adjust left in a voice (read back; waits for the context's work in flight): *has_nfc <- VoiceFlag::HasNfc,
+ * coeffs[14] <- the voice's a[o][0] and b[o][1..o] in oalgpu_channel_source_nfc_host's order.  Near-field contexts only. */
+int oalgpu_voice_nfc_readback(oalgpu_context *ctx, uint32_t voice, int32_t *has_nfc, float *coeffs);
 
 /* One update: zero the dry/real and wet buses, mix every Playing|Stopping voice
  * (Voice::mix, core/voice.cpp:988-1233), and -- HRTF context, post_process != 0 -- run

@@ -39,7 +39,7 @@
 #include "../host/tables.hpp"
 #include "api_util.hpp"
 #include "kernels.hpp"
-#include "dev_source_channels.hpp"
+#include "dev_source_nfc.hpp"
 #include "bus_merge.hpp"
 #include "reverb_dev.hpp"
 
@@ -188,6 +188,8 @@ struct oalgpu_context {
     DevBuf<AmbiScaleState> ambi;
     DevBuf<NfcState> nfc;
     NfcDesign nfcDevice{};                   // DeviceBase::mNFCtrlFilter (after init(w1))
+    float nfcAvgDist{0.0f};                  // DeviceBase::AvgSpeakerDist (oalgpu_context_set_nfc_distance; 0: not told)
+    DevBuf<NfcRecord> nfcRecDev;             // the source stage's NFC records of a synchronous call (SourceNfcKernel -> ApplyNfcKernel)
     DevBuf<unsigned long long> phaseTimes;  // OALGPU_CTX_PROFILE: the measurement variant's stamps
     WaveProf prof{nullptr, 0u};
     const WaveProf *profArg() const { return prof.times ? &prof : nullptr; }
@@ -385,6 +387,8 @@ struct oalgpu_param_block {
                                                             // voice kernel's wavefront finds the records of the voices it mixed
     uint32_t mapVoices{0};
     DevBuf<float> rows;                                     // [record][irStride][2]: the records' blended target HRIRs (resident contexts)
+    DevBuf<NfcRecord> nfc;                                  // [record]: the records' NfcFilter adjusts (blocks made from sources on a
+                                                            // near-field context; null otherwise), installed with the records
     std::vector<std::pair<uint32_t, uint32_t>> cbSteps;     // (voice, mStep) of the callback voices in the block
     oalgpu_context *heldBy{nullptr};                        // a resident context that keeps the block for its next update (res.pendingBlock)
 };
@@ -456,6 +460,10 @@ void PendStart(oalgpu_context *c, const VoiceInitRecord &rec);
 // a parameter block whose records are in place: its voice -> record map and, where the voice kernel installs blocks, its rows
 int FinishParamBlock(oalgpu_context *c, struct oalgpu_param_block *b, const uint32_t *voices, size_t count);
 oalgpu::HrtfStoreDev HostStoreView(const oalgpu::HrtfData &h);     // api_hrtf.hip
+// a near-field context's side of the source stage (api_sources.hip): what SourceNfcKernel reads of the context, and the install
+// of `count` NFC records behind the parameter records they belong to
+oalgpu::NfcSetup NfcSetupOf(const oalgpu_context *c);
+void ApplyNfcRecords(oalgpu_context *c, const oalgpu::NfcRecord *recs, uint32_t count);
 int ServiceCallbacks(oalgpu_context *c, uint32_t samplesToDo);     // api_callback.hip
 int CommReduceBus(oalgpu_context *c, hipStream_t s);               // api_comm.hip
 

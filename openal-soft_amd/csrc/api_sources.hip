@@ -1,7 +1,9 @@
 // 3D source parameters computed on the GPU: the listener, the slots' send environments, and the entry points that turn source
 // properties into parameter records with SourceParamsKernel (source_kernels.hip) -- and the same arithmetic (dev_source.hpp)
 // compiled for the host, oalgpu_source_params_host.  The same for multi-channel and non-spatialized sources: channel sources,
-// ChannelParamsKernel (source_channel_kernels.hip), dev_source_channels.hpp, oalgpu_channel_source_params_host.
+// ChannelParamsKernel (source_channel_kernels.hip), dev_source_channels.hpp, oalgpu_channel_source_params_host.  On a context with
+// near-field control that knows its speaker distance the same entry points also run the near-field side: SourceNfcKernel and
+// ApplyNfcKernel (source_nfc_kernels.hip), dev_source_nfc.hpp, oalgpu_channel_source_nfc_host.
 #include "api_context.hpp"
 
 namespace {
@@ -59,13 +61,22 @@ SourceSetup SetupOf(const oalgpu_context *c)
         c->slotEnv.p, c->rsConsts.p, c->dryMap.p, c->wetMaps.p};
 }
 
+// the near-field side of a call (contexts with near-field control): SourceNfcKernel over the staged records the params kernel
+// of the same call reads -- `mono` or `chan`, the other null -- into `out`, on the context's stream beside it
+int RunNfcStage(oalgpu_context *c, const SourceRecord *mono, const ChannelSourceRecord *chan, size_t sources, NfcRecord *out)
+{
+    LaunchSourceNfc(c->stream, SetupOf(c), c->listener, NfcSetupOf(c), mono, chan, uint32_t(sources), out);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
 // what both entry points refuse, and the source records of what they accept (c->srcHost)
 int CollectSources(oalgpu_context *c, const char *who, const uint32_t *voices, const oalgpu_source_props *props, size_t count)
 {
     const std::string name(who);
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, name + ": HRTF context without a data set");
-    if(c->L.nfc)
-        return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control (the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
+    if(c->L.nfc && !(c->nfcAvgDist > 0.0f))
+        return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control whose speaker distance is not set (oalgpu_context_set_nfc_distance; without it the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
     for(size_t i = 0; i < count; ++i)
     {
         if(voices[i] >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, name + ": bad voice index");
@@ -95,8 +106,8 @@ int CollectChannelSources(oalgpu_context *c, const char *who, const oalgpu_chann
 {
     const std::string name(who);
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, name + ": HRTF context without a data set");
-    if(c->L.nfc)
-        return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control (the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
+    if(c->L.nfc && !(c->nfcAvgDist > 0.0f))
+        return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control whose speaker distance is not set (oalgpu_context_set_nfc_distance; without it the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
     std::vector<uint8_t> named(c->L.numVoices, 0);
     c->chanHost.clear(); c->srcVoices.clear();
     for(size_t i = 0; i < count; ++i)
@@ -214,6 +225,20 @@ void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const
 
 } // namespace
 
+NfcSetup NfcSetupOf(const oalgpu_context *c)
+{
+    const NfcDesign &d = c->nfcDevice;
+    return NfcSetup{c->nfcAvgDist, {d.baseGain[1], d.baseGain[2], d.baseGain[3], d.baseGain[4]}};
+}
+
+void ApplyNfcRecords(oalgpu_context *c, const NfcRecord *recs, uint32_t count)
+{
+    NfcDeviceCoeffs a{};
+    for(uint32_t o = 1; o <= 4u; ++o)
+        for(uint32_t k = 1; k <= o; ++k) a.a[NfcPacked(o, k)] = c->nfcDevice.a[o][k];
+    LaunchApplyNfc(c->stream, c->L, a, recs, count);
+}
+
 int oalgpu_context_set_listener(oalgpu_context *c, const oalgpu_listener_params *listener)
 {
     if(!c || !listener) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_set_listener: null argument");
@@ -244,10 +269,13 @@ int oalgpu_voice_set_source_props(oalgpu_context *c, const uint32_t *voices, con
     count = c->srcHost.size();
     if(int rc = StageRecords(c->stream, c->srcDev, c->srcHost.data(), count)) return rc;
     if(c->paramDev.n < count) HIP_TRY(c->paramDev.alloc(count));
+    if(c->L.nfc && c->nfcRecDev.n < count) HIP_TRY(c->nfcRecDev.alloc(count));
     LaunchSourceParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->srcDev.p, uint32_t(count), c->paramDev.p);
     HIP_TRY(hipGetLastError());
+    if(c->L.nfc) { if(int rc = RunNfcStage(c, c->srcDev.p, nullptr, count, c->nfcRecDev.p)) return rc; }
     LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(count));
     HIP_TRY(hipGetLastError());
+    if(c->L.nfc) { ApplyNfcRecords(c, c->nfcRecDev.p, uint32_t(count)); HIP_TRY(hipGetLastError()); }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return OALGPU_OK;
 }
@@ -269,8 +297,10 @@ int oalgpu_param_block_create_from_sources(oalgpu_context *c, const uint32_t *vo
     b->hrtfGeneration = c->hrtfGeneration;
     HIP_TRY(b->recs.alloc(count));
     if(int rc = StageRecords(c->stream, c->srcDev, c->srcHost.data(), count)) return rc;
+    if(c->L.nfc) HIP_TRY(b->nfc.alloc(count));
     LaunchSourceParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->srcDev.p, uint32_t(count), b->recs.p);
     HIP_TRY(hipGetLastError());
+    if(c->L.nfc) { if(int rc = RunNfcStage(c, c->srcDev.p, nullptr, count, b->nfc.p)) return rc; }
     HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
     if(int rc = FinishParamBlock(c, b.get(), voices, count)) return rc;
     *out = b.release();
@@ -317,9 +347,12 @@ int oalgpu_voice_set_channel_sources(oalgpu_context *c, const oalgpu_channel_sou
     if(int rc = EnsureSourceStage(c)) return rc;
     const size_t records = c->srcVoices.size();
     if(c->paramDev.n < records) HIP_TRY(c->paramDev.alloc(records));
+    if(c->L.nfc && c->nfcRecDev.n < records) HIP_TRY(c->nfcRecDev.alloc(records));
     if(int rc = RunChannelStage(c, c->paramDev.p)) return rc;
+    if(c->L.nfc) { if(int rc = RunNfcStage(c, nullptr, c->chanDev.p, c->chanHost.size(), c->nfcRecDev.p)) return rc; }
     LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(records));
     HIP_TRY(hipGetLastError());
+    if(c->L.nfc) { ApplyNfcRecords(c, c->nfcRecDev.p, uint32_t(records)); HIP_TRY(hipGetLastError()); }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return OALGPU_OK;
 }
@@ -339,7 +372,9 @@ int oalgpu_param_block_create_from_channel_sources(oalgpu_context *c, const oalg
     b->device = c->desc.device;
     b->hrtfGeneration = c->hrtfGeneration;
     HIP_TRY(b->recs.alloc(records));
+    if(c->L.nfc) HIP_TRY(b->nfc.alloc(records));
     if(int rc = RunChannelStage(c, b->recs.p)) return rc;
+    if(c->L.nfc) { if(int rc = RunNfcStage(c, nullptr, c->chanDev.p, c->chanHost.size(), b->nfc.p)) return rc; }
     HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
     if(int rc = FinishParamBlock(c, b.get(), c->srcVoices.data(), records)) return rc;
     *out = b.release();
@@ -375,6 +410,41 @@ int oalgpu_channel_source_params_host(const oalgpu_context_desc *desc, const oal
             oalgpu_voice_params &o = out[i * OALGPU_MAX_SOURCE_CHANNELS + ch];
             if(ch >= SourceChannelCount(src.channels)) std::memset(&o, 0, sizeof(o));
             else FillVoiceParams(o, src.props, g, ChannelPanning(ChannelSeatOf(src.channels, ch, stereoPan, src.panning), g, h.cx.hrtf), h);
+        }
+    }
+    return OALGPU_OK;
+}
+
+int oalgpu_channel_source_nfc_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
+    const oalgpu_slot_environment *slots, float avg_speaker_dist, uint32_t frequency, const oalgpu_channel_source *sources,
+    size_t count, float *w0, float *coeffs)
+{
+    HostStage h;
+    if(int rc = h.build("oalgpu_channel_source_nfc_host", desc, listener, slots, nullptr, nullptr, nullptr, nullptr, nullptr, 0, frequency,
+        sources && w0 && coeffs && avg_speaker_dist > 0.0f && desc && !desc->hrtf))
+        return rc;
+    for(size_t i = 0; i < count; ++i)
+    {
+        const oalgpu_channel_source &src = sources[i];
+        if(src.channels < OALGPU_CHANNELS_MONO || src.channels > OALGPU_CHANNELS_X71 || src.spatialize < OALGPU_SPATIALIZE_OFF
+            || src.spatialize > OALGPU_SPATIALIZE_AUTO)
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_nfc_host: channels or spatialize out of range");
+        if(!PropsOk(src.props, h.cx.numSends, h.cx.numSlots))
+            return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_nfc_host: resampler, distance model or send slot out of range");
+    }
+    NfcDesign device;
+    NfcInit(343.3f / avg_speaker_dist / float(desc->sample_rate), device);        // InitNearFieldCtrl's w1, in its operation order
+    for(size_t i = 0; i < count; ++i)
+    {
+        const oalgpu_channel_source &src = sources[i];
+        const float distance = SourceRoute(src.channels, src.spatialize) ? SourceAttenuation(src.props, frequency, *listener, h.cx).distance : 0.0f;
+        w0[i] = SourceNfcW0(distance, listener->nfc_scale, avg_speaker_dist, desc->sample_rate);
+        float *o = coeffs + i * 14;
+        for(uint32_t order = 1; order <= 4u; ++order)
+        {
+            float b[5];
+            o[order - 1u] = device.baseGain[order] * NfcOrderDesign(order, w0[i], b);
+            for(uint32_t k = 1; k <= order; ++k) o[4u + NfcPacked(order, k)] = b[k];
         }
     }
     return OALGPU_OK;

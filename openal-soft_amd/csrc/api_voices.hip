@@ -149,6 +149,17 @@ int oalgpu_context_set_nfc(oalgpu_context *c, float w1, const uint32_t channels_
     return OALGPU_OK;
 }
 
+int oalgpu_context_set_nfc_distance(oalgpu_context *c, float avg_speaker_dist)
+{
+    if(!c || !(avg_speaker_dist > 0.0f) || !(avg_speaker_dist < __builtin_inff()))
+        return Fail(OALGPU_ERR_INVALID, "oalgpu_context_set_nfc_distance: bad arguments");
+    if(!c->L.nfc) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_set_nfc_distance: oalgpu_context_set_nfc first");
+    if(int rc = UseCtx(c)) return rc;
+    if(int rc = oalgpu_sync(c)) return rc;
+    c->nfcAvgDist = avg_speaker_dist;            // (a kernel argument of the source stage's launches from now on)
+    return OALGPU_OK;
+}
+
 int oalgpu_voice_set_nfc(oalgpu_context *c, uint32_t voice, float w0)
 {
     if(!VoiceOk(c, voice) || !(w0 >= 0.0f)) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_nfc: bad arguments");
@@ -161,6 +172,38 @@ int oalgpu_voice_set_nfc(oalgpu_context *c, uint32_t voice, float w0)
     std::memcpy(st.b, d.b, sizeof(st.b));
     LaunchSetNfc(c->stream, c->L, voice, st);
     HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+// oalgpu_voice_set_nfc's host arithmetic by itself: init(w1), adjust(w0), what the voice would get
+int oalgpu_nfc_adjust_host(float w1, float w0, float *coeffs)
+{
+    if(!(w1 > 0.0f) || !(w0 >= 0.0f) || !coeffs) return Fail(OALGPU_ERR_INVALID, "oalgpu_nfc_adjust_host: bad arguments");
+    NfcDesign d;
+    NfcInit(w1, d);
+    NfcAdjust(w0, d);
+    for(uint32_t o = 1; o <= 4u; ++o)
+    {
+        coeffs[o - 1u] = d.a[o][0];
+        for(uint32_t k = 1; k <= o; ++k) coeffs[4u + NfcPacked(o, k)] = d.b[o][k];
+    }
+    return OALGPU_OK;
+}
+
+int oalgpu_voice_nfc_readback(oalgpu_context *c, uint32_t voice, int32_t *has_nfc, float *coeffs)
+{
+    if(int rc = BeginVoiceCall(c, VoiceOk(c, voice) && has_nfc && coeffs, "oalgpu_voice_nfc_readback", true)) return rc;
+    if(!c->L.nfc) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_nfc_readback: oalgpu_context_set_nfc first");
+    NfcState st{};
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&st, c->nfc.p + voice, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&flags, &c->ctl.p[voice].flags, sizeof(flags), hipMemcpyDeviceToHost));
+    *has_nfc = (flags & kFlagNfc) ? 1 : 0;
+    for(uint32_t o = 1; o <= 4u; ++o)
+    {
+        coeffs[o - 1u] = st.a[o][0];
+        for(uint32_t k = 1; k <= o; ++k) coeffs[4u + NfcPacked(o, k)] = st.b[o][k];
+    }
     return OALGPU_OK;
 }
 
@@ -315,7 +358,8 @@ int oalgpu_param_block_apply(oalgpu_context *c, oalgpu_param_block *b)
         b->heldBy = c;
         return OALGPU_OK;
     }
-    if(c->pendingMix.active && b->mapVoices == c->L.numVoices && WaveKernelAppliesRecords(c->L) && c->initPending.empty())
+    // (a block with NFC records goes the launched way: no voice kernel installs those)
+    if(c->pendingMix.active && b->mapVoices == c->L.numVoices && WaveKernelAppliesRecords(c->L) && c->initPending.empty() && !b->nfc.p)
     {   // the update submitted last has not been launched yet: its voice kernel installs this block (see pendingMix)
         if(int rc = UseDevice(c->desc.device)) return rc;
         if(int rc = FlushPendingMix(c, b)) return rc;
@@ -325,6 +369,7 @@ int oalgpu_param_block_apply(oalgpu_context *c, oalgpu_param_block *b)
     if(int rc = BeginVoiceCall(c)) return rc;
     LaunchApplyParams(c->stream, c->L, b->recs.p, b->count);
     HIP_TRY(hipGetLastError());
+    if(b->nfc.p && c->L.nfc) { ApplyNfcRecords(c, b->nfc.p, b->count); HIP_TRY(hipGetLastError()); }
     }
     for(const auto &vs : b->cbSteps)
         if(vs.first < c->cbOfVoice.size() && c->cbOfVoice[vs.first] >= 0) c->cbVoices[size_t(c->cbOfVoice[vs.first])].step = vs.second;

@@ -5,6 +5,8 @@
 // DesignBiquad (BiquadFilter::SetParams, rcpQ given), DesignBiquadFromSlope (setParamsFromSlope) and BsincPrepare's scale:
 // compiled here for the host and by csrc/source_kernels.hip for the device
 #include "../csrc/dev_design.hpp"
+// NfcFilter's sections (NfcInit, NfcAdjust): compiled here for the host and by csrc/source_nfc_kernels.hip for the device
+#include "../csrc/dev_nfc_design.hpp"
 
 namespace oalgpu {
 

@@ -208,6 +208,28 @@ def channel_source_params_host(desc, listener, sources_array, frequency, slots=N
                         dry_map, wet_maps, mhr)
 
 
+def channel_source_nfc_host(desc, listener, sources_array, frequency, avg_speaker_dist, slots=None):
+    """oalgpu_channel_source_nfc_host: the near-field side of the source stage compiled for the host (no device), for a ctypes array
+    of ChannelSource on a context of `desc` whose speakers are avg_speaker_dist away
+    -> (w0[n], coeffs[n, 14]: a[o][0] of the orders 1..4, then b[1][1], b[2][1..2], b[3][1..3], b[4][1..4]) as float32 arrays"""
+    n = len(sources_array)
+    w0 = np.zeros(n, np.float32)
+    coeffs = np.zeros((n, 14), np.float32)
+    fn = lib.oalgpu_channel_source_nfc_host
+    fn.argtypes = [C.POINTER(ContextDesc), C.POINTER(ListenerParams), C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_size_t, f32p, f32p]
+    check(fn(C.byref(desc), C.byref(listener), C.cast(slots, C.c_void_p) if slots is not None else None, avg_speaker_dist, frequency,
+             C.cast(sources_array, C.c_void_p), n, _fp(w0), _fp(coeffs)), "oalgpu_channel_source_nfc_host")
+    return w0, coeffs
+
+
+def nfc_adjust_host(w1, w0):
+    """oalgpu_nfc_adjust_host: what oalgpu_voice_set_nfc(voice, w0) designs on a context of oalgpu_context_set_nfc(w1) -> coeffs[14]"""
+    coeffs = np.zeros(14, np.float32)
+    lib.oalgpu_nfc_adjust_host.argtypes = [C.c_float, C.c_float, f32p]
+    check(lib.oalgpu_nfc_adjust_host(w1, w0, _fp(coeffs)), "oalgpu_nfc_adjust_host")
+    return coeffs
+
+
 class VoiceState(C.Structure):
     _fields_ = [("play_state", C.c_int32), ("position", C.c_int32), ("position_frac", C.c_uint32),
                 ("has_buffer", C.c_int32), ("fading", C.c_int32),
@@ -733,6 +755,18 @@ class Scene:
     def set_voice_nfc(self, voice, w0):
         lib.oalgpu_voice_set_nfc.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
         check(lib.oalgpu_voice_set_nfc(self.h, voice, w0), "oalgpu_voice_set_nfc")
+
+    def set_nfc_distance(self, avg_speaker_dist):
+        """DeviceBase::AvgSpeakerDist: from here on the source entry points compute the voices' w0 and NfcFilter adjust themselves"""
+        lib.oalgpu_context_set_nfc_distance.argtypes = [C.c_void_p, C.c_float]
+        check(lib.oalgpu_context_set_nfc_distance(self.h, avg_speaker_dist), "oalgpu_context_set_nfc_distance")
+
+    def voice_nfc(self, voice):
+        """(VoiceFlag::HasNfc, the 14 adjusted coefficients in channel_source_nfc_host's order) of a voice, read back"""
+        lib.oalgpu_voice_nfc_readback.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), f32p]
+        has, coeffs = C.c_int32(0), np.zeros(14, np.float32)
+        check(lib.oalgpu_voice_nfc_readback(self.h, voice, C.byref(has), _fp(coeffs)), "oalgpu_voice_nfc_readback")
+        return bool(has.value), coeffs
 
     # B-Format sources: one voice per channel over channel views of the interleaved buffer
     # (same interface as tests/oracle_lib.Scene: `voice` = what add_ambi_voice returned)
