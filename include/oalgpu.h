@@ -197,7 +197,23 @@ typedef struct oalgpu_context_desc {
                                    * context, and when that call is oalgpu_param_block_apply the update's own voice kernel installs the
                                    * block (every wavefront the records of the voices it mixed) instead of a parameter kernel between
                                    * two voice kernels.  Measured slower than the parameter kernel on three of five boxes (DESIGN.md
-                                   * 3.10): an opt-in variant, for A/B runs */
+                                   * 3.10): an opt-in variant, for A/B runs.
+                                   * Where the voice kernel has a bounded-run form (HRTF contexts on the voice-per-wavefront kernel, no
+                                   * sends) ONE launch may cover up to four such deferred updates, update by update, each with its own
+                                   * block, reduction, post-process and output: an update whose block has been handed over waits for
+                                   * the next while the main stream is still busy with the launch before (oalgpu_context_set_launch_span).
+                                   * A deferred update may therefore leave up to four calls late; any call that needs it -- every setter,
+                                   * oalgpu_sync, every read-back, the timing mode, the context's or a queued block's destruction --
+                                   * submits what waits first, so results and their order are those of a launch per update
+                                   * (tests/test_gpu_launch_span.py) */
+#define OALGPU_CTX_SPAN_ONE 1024u /* OALGPU_CTX_APPLY_IN_VOICE_KERNEL contexts: never more than one update per voice launch
+                                   * (oalgpu_context_set_launch_span(ctx, 1) from the start, without the extra partial-bus sets) -- for A/B runs */
+#define OALGPU_CTX_FULL_POST 2048u /* OALGPU_CTX_APPLY_IN_VOICE_KERNEL contexts: keep the reduction and the whole post-process (band split, decoder FIR,
+                                   * shift) as the two launches of every update.  Without the flag an update whose dry lines have no
+                                   * writer -- no effect slots, no collective, no limiter, never an attached context, the bus pointer never
+                                   * handed out -- runs ONE launch that reduces the accumulator, forms the two output lines and shifts the
+                                   * accumulator: the post-process of silent dry lines adds exactly nothing, so the numbers are the same
+                                   * (tests/test_gpu_silent_post.py).  For A/B runs and tests */
 #define OALGPU_CTX_FUSED_REDUCE 32u /* pipelined HRTF contexts without effect slots and without a collective: the bus reduction and the
                                    * post-process as ONE launch.  One launch less for the host, and measured 1.2-1.9 us per update
                                    * slower than the two launches: an opt-in variant, for A/B runs */
@@ -615,6 +631,15 @@ int oalgpu_voice_nfc_readback(oalgpu_context *ctx, uint32_t voice, int32_t *has_
  * MixDirectHrtf over the dry bus (DeviceBase::Process(HrtfPostProcess), alc/alu.cpp:289-298).
  * Asynchronous on the context's stream; oalgpu_sync() or a read-back waits. */
 int oalgpu_mix_update(oalgpu_context *ctx, uint32_t samples_to_do, int post_process);
+/* How many deferred updates (OALGPU_CTX_APPLY_IN_VOICE_KERNEL) one voice launch covers.  0, the default: as many as the host has
+ * handed over while the main stream was busy, four at most -- a host that reads every update back gets a launch per update, one
+ * that runs ahead of the GPU gets launches that span its lead.  1: never more than one.  2 .. 4: exactly that many, waited for
+ * even on an idle GPU (anything that flushes submits fewer); for tests.  Contexts without the bounded-run kernel ignore it. */
+int oalgpu_context_set_launch_span(oalgpu_context *ctx, uint32_t n);
+/* What the pipelined updates submitted so far were launched as (updates still deferred are not counted; nothing is flushed):
+ * spans[i] = voice launches that covered i + 1 updates; *silent_posts = updates whose reduction and post-process were the one
+ * launch of a context whose dry lines have no writer (see OALGPU_CTX_FULL_POST).  Either pointer may be NULL. */
+int oalgpu_context_launch_stats(oalgpu_context *ctx, uint64_t spans[4], uint64_t *silent_posts);
 int oalgpu_sync(oalgpu_context *ctx);
 /* OALGPU_CTX_RESIDENT: what the mode has done so far.  timed_*: launches that have ended -- their own durations (HIP events
  * bound to the dispatch) and the updates they covered; timed_kernel_ms / timed_updates is the voice kernel's time per update. */

@@ -178,7 +178,9 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prioGreatest));
     HIP_TRY(hipEventCreate(&c->evStart)); HIP_TRY(hipEventCreate(&c->evVoice)); HIP_TRY(hipEventCreate(&c->evEnd));
     HIP_TRY(hipStreamCreateWithPriority(&c->postStream, hipStreamDefault, prioLeast));
-    for(hipEvent_t *e : {&c->evVoiceDone[0], &c->evVoiceDone[1], &c->evReduceDone[0], &c->evReduceDone[1], &c->evPostDone})
+    std::vector<hipEvent_t*> orderEvents{&c->evVoiceDone[0], &c->evVoiceDone[1], &c->evPostDone};
+    for(hipEvent_t &e : c->evReduceDone) orderEvents.push_back(&e);
+    for(hipEvent_t *e : orderEvents)
         // ordering between the context's two streams only: no system-scope fence (the default one
         // costs ~3.5 us of cache write-back per record on the stream it sits in -- measured, tools/
         // step_period.py; hosts and peers see the results through oalgpu_sync / stream order as before)
@@ -288,6 +290,14 @@ int oalgpu_context_create(const oalgpu_context_desc *desc, oalgpu_context **out)
     HIP_TRY(c->partHrtf.alloc(L.hrtf ? groups * (kLine + kHrirLen) * 2 : 0)); L.partHrtf = c->partHrtf.p;
     HIP_TRY(c->partHrtf2.alloc(c->useWave && L.hrtf ? groups * (kLine + kHrirLen) * 2 : 0));
     c->partHrtfBuf[0] = c->partHrtf.p; c->partHrtfBuf[1] = c->partHrtf2.p;
+    if(c->useWave && L.hrtf && L.numSends == 0 && (desc->flags & OALGPU_CTX_APPLY_IN_VOICE_KERNEL) && !(desc->flags & OALGPU_CTX_SPAN_ONE))
+    {   // a voice launch of such a context may cover up to kSpanMax deferred updates, each with a partial set of its own: sets for two launches in flight
+        const size_t setFloats = groups * (kLine + kHrirLen) * 2;
+        HIP_TRY(c->partHrtfMore.alloc(setFloats * (oalgpu_context::kPartSets - 2u)));
+        for(uint32_t k = 2; k < oalgpu_context::kPartSets; ++k) c->partHrtfBuf[k] = c->partHrtfMore.p + setFloats * (k - 2u);
+        c->numSets = oalgpu_context::kPartSets;
+    }
+    if(desc->flags & OALGPU_CTX_SPAN_ONE) c->launchSpan = 1u;
     HIP_TRY(c->bus.alloc(BusFloats(L))); HIP_TRY(c->bus.zero()); L.bus = c->bus.p;
     if(desc->flags & OALGPU_CTX_PROFILE)
     {
@@ -426,6 +436,31 @@ int PostDirectHrtfFused(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do
     return OALGPU_OK;
 }
 
+// The held reduction of an update whose dry lines have no writer (RunMixUpdate: silentPost), with what is left of its post-process
+// in the same launch (BusReduceShiftKernel, voice_kernel.hip).  The carried accumulator alternates between carryBuf and the bus
+// block's accumulator region: the launch reads one and files the shifted one in the other, and carryInBuf says where it is --
+// to the next reduction of either path (CarrySource) and to oalgpu_read_hrtf_accum.  No PostFusedKernel runs: its channel counter
+// (postEpoch) and the splitter states (dSplitCur) stay where they are.
+static int ReduceShiftSilent(oalgpu_context *c, hipStream_t s, uint32_t samples_to_do, hipEvent_t evDone)
+{
+    c->reduceHeld = false;
+    float *left = c->L.bus + size_t{c->L.numDry} * kLine;
+    const uint32_t slot = c->outNext % oalgpu_context::kIoSlots;
+    const bool ring = c->outRing && c->outFlags;
+    const uint32_t outTarget = c->outArrivedTotal + BusReduceShiftGroups();
+    const bool wasInBuf = c->carryInBuf;
+    const float *carry = CarrySource(c, c->carryAccum);
+    float *carryOut = wasInBuf ? c->L.bus + BusAccumOffset(c->L) : c->carryBuf.p;
+    LaunchBusReduceShift(s, c->heldL, carry, carryOut, left, left + kLine, samples_to_do, evDone, ring ? c->outHost[slot] : nullptr,
+        ring ? c->outFlags + size_t{slot} * 16 : nullptr, c->outSeq + 1u, c->outArrived.p, outTarget);
+    HIP_TRY(hipGetLastError());
+    if(ring) { c->outArrivedTotal = outTarget; c->outSlotSeq[slot] = ++c->outSeq; }
+    c->outRingWritten = ring;
+    c->carryInBuf = !wasInBuf;
+    ++c->silentPosts;
+    return OALGPU_OK;
+}
+
 // Orders the main stream behind whatever a pipelined oalgpu_mix_update left on the post stream.
 int JoinPost(oalgpu_context *c)
 {
@@ -536,6 +571,19 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
 }
 
 static int RunMixUpdate(oalgpu_context *c, uint32_t samples_to_do, int post_process, oalgpu_param_block *next);
+static void PlanPost(oalgpu_context *c, int post_process);
+static int GuardPartialSet(oalgpu_context *c, uint32_t p);
+static int ReduceBehindVoices(oalgpu_context *c, const DeviceLayout &L, uint32_t p, uint32_t samples_to_do);
+
+// How many deferred updates ONE voice launch of the context may cover right now (1: a launch per update).  A launch spans updates
+// only where nothing has to happen on the host or on another context between two of them: no callback sources, no attached
+// contexts, no collective, no deferred starts, no measurement variant.
+static uint32_t SpanLimit(const oalgpu_context *c)
+{
+    if(c->launchSpan == 1u || c->numSets < oalgpu_context::kPartSets || !Wave16HasSpan(c->L)) return 1u;
+    if(!c->cbVoices.empty() || !c->attached.empty() || c->attachedTo || c->comm || c->timing || !c->initPending.empty() || c->prof.times) return 1u;
+    return c->launchSpan ? c->launchSpan : kSpanMax;
+}
 
 int oalgpu_mix_update(oalgpu_context *c, uint32_t samples_to_do, int post_process)
 {
@@ -546,14 +594,56 @@ int oalgpu_mix_update(oalgpu_context *c, uint32_t samples_to_do, int post_proces
         const int rc = ResidentSubmit(c, samples_to_do);
         if(rc <= 0) return rc;                       // (1: the mode is not available after all -- on to the launched path)
     }
-    if(int rc = UseCtx(c)) return rc;                // (submits the update deferred before this one)
-    if(c->useWave && c->ownStream && !c->serialOnly && !c->timing && (c->desc.flags & OALGPU_CTX_APPLY_IN_VOICE_KERNEL) && WaveKernelAppliesRecords(c->L)
-        && !(c->res.enabled && !c->res.failed && !c->res.cooldown))
-    {   // submitted with the next library call on this context (see pendingMix); whatever goes wrong then is that call's error
-        c->pendingMix.active = true; c->pendingMix.samples = samples_to_do; c->pendingMix.post = post_process;
+    const bool defers = c->useWave && c->ownStream && !c->serialOnly && !c->timing && (c->desc.flags & OALGPU_CTX_APPLY_IN_VOICE_KERNEL)
+        && WaveKernelAppliesRecords(c->L) && !(c->res.enabled && !c->res.failed && !c->res.cooldown);
+    // deferred updates whose blocks have all been handed over, and room in the launch that will cover them: this one joins them
+    auto &Q = c->pendingMix;
+    if(defers && Q.count && Q.count < SpanLimit(c) && Q.u[Q.count - 1u].behind && !c->res.pendingBlock)
+    {
+        if(int rc = UseDevice(c->desc.device)) return rc;
+        Q.u[Q.count++] = oalgpu_context::PendingUpdate{samples_to_do, post_process, nullptr};
+        return OALGPU_OK;
+    }
+    if(int rc = UseCtx(c)) return rc;                // (submits the updates deferred before this one)
+    if(defers)
+    {   // submitted with a later library call on this context (see pendingMix); whatever goes wrong then is that call's error
+        Q.u[0] = oalgpu_context::PendingUpdate{samples_to_do, post_process, nullptr};
+        Q.count = 1;
         return OALGPU_OK;
     }
     return RunMixUpdate(c, samples_to_do, post_process, nullptr);
+}
+
+int oalgpu_context_set_launch_span(oalgpu_context *c, uint32_t n)
+{
+    if(int rc = BeginSetter(c, "oalgpu_context_set_launch_span")) return rc;
+    if(n > kSpanMax) return Fail(OALGPU_ERR_INVALID, "oalgpu_context_set_launch_span: 0 (automatic), 1 (never) or 2 .. 4 updates per launch");
+    c->launchSpan = n;
+    return OALGPU_OK;
+}
+
+int oalgpu_context_launch_stats(oalgpu_context *c, uint64_t spans[4], uint64_t *silent_posts)
+{
+    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
+    static_assert(kSpanMax == 4, "oalgpu.h says four");
+    if(spans) for(uint32_t i = 0; i < kSpanMax; ++i) spans[i] = c->spanCounts[i];
+    if(silent_posts) *silent_posts = c->silentPosts;
+    return OALGPU_OK;
+}
+
+// oalgpu_param_block_apply on a context whose newest deferred update has no block behind it yet: the block goes there, and the
+// queue is submitted if the launch that covers it is full -- or, under the automatic rule, if the main stream has nothing to do
+// (the last voice launch has ended: holding updates back would leave the GPU idle).  A host that waits for every update's output
+// thus gets a launch per update; one that runs ahead of the GPU gets launches that span its lead.
+int DeferBlockBehindPending(oalgpu_context *c, oalgpu_param_block *b)
+{
+    auto &Q = c->pendingMix;
+    Q.u[Q.count - 1u].behind = b;
+    b->queuedBy = c;
+    bool submit = Q.count >= SpanLimit(c);
+    if(!submit && c->launchSpan == 0u)
+        submit = !c->lastVoiceEvent || hipEventQuery(c->lastVoiceEvent) != hipErrorNotReady;
+    return submit ? FlushPendingMix(c) : OALGPU_OK;
 }
 
 int BeginSetter(oalgpu_context *c, const char *who)
@@ -563,13 +653,19 @@ int BeginSetter(oalgpu_context *c, const char *who)
     return c->res.pendingBlock ? UseCtx(c) : OALGPU_OK;
 }
 
-int FlushPendingMix(oalgpu_context *c, oalgpu_param_block *next)
+static int RunMixSpan(oalgpu_context *c, const oalgpu_context::PendingUpdate *u, uint32_t count);
+
+int FlushPendingMix(oalgpu_context *c)
 {
     // (a setter of an attached context: the device context's deferred update mixes this context's voices as they were)
     if(c->attachedTo) { if(int rc = FlushPendingMix(c->attachedTo)) return rc; }
-    if(!c->pendingMix.active) return OALGPU_OK;
-    c->pendingMix.active = false;
-    return RunMixUpdate(c, c->pendingMix.samples, c->pendingMix.post, next);
+    if(!c->pendingMix.active()) return OALGPU_OK;
+    const auto Q = c->pendingMix;
+    c->pendingMix.count = 0;
+    for(uint32_t i = 0; i < Q.count; ++i) if(Q.u[i].behind) Q.u[i].behind->queuedBy = nullptr;
+    if(Q.count > 1u && Q.count <= SpanLimit(c)) return RunMixSpan(c, Q.u, Q.count);
+    for(uint32_t i = 0; i < Q.count; ++i) { if(int rc = RunMixUpdate(c, Q.u[i].samples, Q.u[i].post, Q.u[i].behind)) return rc; }
+    return OALGPU_OK;
 }
 
 // next: a parameter block the update's voice kernel installs behind the voices it mixed (null: none)
@@ -586,13 +682,95 @@ static int RunMixUpdate(oalgpu_context *c, uint32_t samples_to_do, int post_proc
         if(post_process && c->commRank == 0) return oalgpu_post_process(c, samples_to_do);
         return OALGPU_OK;
     }
-    c->fuseReduce = post_process && !c->comm && c->L.hrtf && c->L.numSlots == 0 && c->L.numReal >= 2 && !c->timing
-        && (c->desc.flags & OALGPU_CTX_FUSED_REDUCE) && c->attached.empty();
+    PlanPost(c, post_process);
+    struct ClearSilent { oalgpu_context *c; ~ClearSilent() { c->silentPost = false; } } clearSilent{c};
     const int rcv = oalgpu_mix_voices_overlapped(c, samples_to_do);
     c->fuseReduce = false;
     if(rcv) { c->reduceHeld = false; return rcv; }
     // sharded contexts: the effects and the post-process run where the reduced buses are, on rank 0
     return oalgpu_post_process_overlapped(c, samples_to_do, post_process && c->commRank == 0);
+}
+
+// how a pipelined update's reduction and post-process are launched: fuseReduce, silentPost
+static void PlanPost(oalgpu_context *c, int post_process)
+{
+    const bool oneLaunch = post_process && !c->comm && c->L.hrtf && c->L.numSlots == 0 && c->L.numReal >= 2 && !c->timing && c->attached.empty();
+    // Nothing writes the dry lines of such a context (the voices mix into the accumulator, the reduction zero-fills the lines), so its
+    // post-process adds nothing: the reduction forms the output lines and shifts the accumulator itself (ReduceShiftSilent).  Sticky:
+    // once something else may have written the lines -- an attached context, a collective, a caller that holds the bus pointer --
+    // the splitters may hold state, and the context keeps the whole chain.
+    // Only where updates are deferred (OALGPU_CTX_APPLY_IN_VOICE_KERNEL): with a parameter kernel between two voice kernels the
+    // short post chain measured 1 us per step SLOWER than the whole one (35.7 -> 36.7 us, profiles/launch_span/fourway_xflags.txt),
+    // and it pays only together with a voice launch that spans updates.
+    if(!c->attached.empty() || c->comm) c->dryWriter = true;
+    c->silentPost = oneLaunch && !c->dryWriter && !c->limOn && (c->desc.flags & OALGPU_CTX_APPLY_IN_VOICE_KERNEL) && !(c->desc.flags & OALGPU_CTX_FULL_POST);
+    c->fuseReduce = c->silentPost || (oneLaunch && (c->desc.flags & OALGPU_CTX_FUSED_REDUCE));
+}
+
+// ONE voice launch over `count` deferred updates (the bounded run of voice_wave16.hip), then on the post stream what each of
+// them has there after a launch of its own, in order: its reduction and its post-process, with its own partial set, events,
+// output lines and ring slot.  What oalgpu_mix_voices_overlapped does in front of a launch is done for every update it covers.
+static int RunMixSpan(oalgpu_context *c, const oalgpu_context::PendingUpdate *u, uint32_t count)
+{
+    if(int rc = UseDevice(c->desc.device)) return rc;
+    if(int rc = FlushResidentBlock(c)) return rc;
+    c->outRingWritten = false;
+    SpanUpdates span{};
+    span.count = count;
+    uint32_t sets[kSpanMax];
+    for(uint32_t i = 0; i < count; ++i)
+    {
+        const uint32_t p = sets[i] = (c->parity + i) % c->numSets;
+        if(int rc = GuardPartialSet(c, p)) return rc;
+        const oalgpu_param_block *b = u[i].behind;
+        span.samples[i] = u[i].samples;
+        span.recs[i] = b ? b->recs.p : nullptr; span.map[i] = b ? b->voiceToRec.p : nullptr; span.rows[i] = b ? b->rows.p : nullptr;
+        span.part[i] = c->partHrtfBuf[p];
+    }
+    hipEvent_t evVoice = c->evVoiceDone[c->voiceLaunches++ & 1u];
+    HIP_TRY(LaunchVoiceWave16Span(c->stream, c->L, span, evVoice));
+    ++c->spanCounts[count - 1u];
+    c->lastVoiceEvent = evVoice;
+    c->parity = (c->parity + count) % c->numSets;
+    HIP_TRY(hipStreamWaitEvent(c->postStream, evVoice, 0));
+    for(uint32_t i = 0; i < count; ++i)
+    {
+        DeviceLayout L = c->L;
+        L.partHrtf = span.part[i];
+        PlanPost(c, u[i].post);
+        struct ClearSilent { oalgpu_context *c; ~ClearSilent() { c->silentPost = false; c->fuseReduce = false; } } clearSilent{c};
+        if(int rc = ReduceBehindVoices(c, L, sets[i], u[i].samples)) { c->reduceHeld = false; return rc; }
+        if(int rc = oalgpu_post_process_overlapped(c, u[i].samples, u[i].post && c->commRank == 0)) return rc;
+    }
+    return OALGPU_OK;
+}
+
+// in front of a voice launch that writes partial set p: the set was last read by the reduction of numSets updates ago
+// (almost always long done: then no barrier packet goes into the main queue in front of the voice kernel)
+static int GuardPartialSet(oalgpu_context *c, uint32_t p)
+{
+    if(c->reduceUpdate[p] > c->updatesKnownDone)
+    {
+        const hipError_t q = hipEventQuery(c->evReduceDone[p]);
+        if(q == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(c->stream, c->evReduceDone[p], 0));
+        else HIP_TRY(q);
+    }
+    c->reduceUpdate[p] = ++c->updatesSubmitted;
+    return OALGPU_OK;
+}
+
+// post stream, behind the wait for the voice launch: the reduction of the update whose partial buses are L's (set p) -- or, held
+// back, its hand-over to the post-process that follows at once and launches it with itself (fuseReduce)
+static int ReduceBehindVoices(oalgpu_context *c, const DeviceLayout &L, uint32_t p, uint32_t samples_to_do)
+{
+    if(c->fuseReduce)
+    {
+        c->reduceHeld = true; c->heldL = L; c->heldParity = p;
+        return OALGPU_OK;
+    }
+    LaunchBusReduce(c->postStream, L, samples_to_do, CarrySource(c, c->carryAccum && L.hrtf), true, c->evReduceDone[p]);
+    HIP_TRY(hipGetLastError());
+    return CommReduceBus(c, c->postStream);                      // beside the next update's voice kernel
 }
 
 /* `count` consecutive updates in one call: update i applies param_blocks[i] (the array or an entry may be NULL) and mixes
@@ -620,38 +798,24 @@ int oalgpu_mix_voices_overlapped(oalgpu_context *c, uint32_t samples_to_do)
     DeviceLayout L = c->L;
     L.partHrtf = c->partHrtfBuf[p];
     if(L.streams || L.accLines || L.rows8) L.partLines = c->partLinesBuf[p];
-    // main stream: this update's voices; its partial-bus buffer was last read by the reduction
-    // of two updates ago
-    // (almost always long done: then no barrier packet goes into the main queue in front of the voice kernel)
-    if(c->reduceUpdate[p] > c->updatesKnownDone)
-    {
-        const hipError_t q = hipEventQuery(c->evReduceDone[p]);
-        if(q == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(c->stream, c->evReduceDone[p], 0));
-        else HIP_TRY(q);
-    }
-    c->reduceUpdate[p] = ++c->updatesSubmitted;
+    // main stream: this update's voices
+    if(int rc = GuardPartialSet(c, p)) return rc;
+    hipEvent_t evVoice = c->evVoiceDone[c->voiceLaunches++ & 1u];
     // (timing: the two events are bound to the dispatch itself -- the kernel's own start and end)
     // The event the post stream waits for is bound to the voice kernel's dispatch (hipExtLaunchKernel's stop event: one
     // runtime call less per update than a record behind the launch).  Timing runs use that slot for their own event.
-    HIP_TRY(LaunchVoiceWave(c->stream, L, samples_to_do, c->profArg(), c->timing ? c->evStart : nullptr, c->timing ? c->evVoice : c->evVoiceDone[p],
+    HIP_TRY(LaunchVoiceWave(c->stream, L, samples_to_do, c->profArg(), c->timing ? c->evStart : nullptr, c->timing ? c->evVoice : evVoice,
         c->nextRecs, c->nextMap, c->nextRows));
-    if(c->timing) HIP_TRY(hipEventRecord(c->evVoiceDone[p], c->stream));
+    if(c->timing) HIP_TRY(hipEventRecord(evVoice, c->stream));
+    ++c->spanCounts[0];
+    c->lastVoiceEvent = evVoice;
     // post stream: the reduction (adds the carried HRTF accumulator tail); whatever follows on that stream -- a collective, the effects, the post-process -- runs beside
     // the next update's parameter and voice kernels
-    HIP_TRY(hipStreamWaitEvent(c->postStream, c->evVoiceDone[p], 0));
+    HIP_TRY(hipStreamWaitEvent(c->postStream, evVoice, 0));
     // (4-wavefront workgroups: they find room on a CU as soon as ONE of the next update's voice workgroups
     // has left it; the 16-wavefront form waits for a whole CU -- measured 62 against 53 us per config-2 step)
-    if(c->fuseReduce)
-    {   // (oalgpu_mix_update: the reduction is launched together with the post-process that follows at once)
-        c->reduceHeld = true; c->heldL = L; c->heldParity = p;
-        c->parity = p ^ 1u;
-        return OALGPU_OK;
-    }
-    LaunchBusReduce(c->postStream, L, samples_to_do, CarrySource(c, c->carryAccum && L.hrtf), true, c->evReduceDone[p]);
-    HIP_TRY(hipGetLastError());
-    if(int rc = CommReduceBus(c, c->postStream)) return rc;      // beside the next update's voice kernel
-    c->parity = p ^ 1u;
-    return OALGPU_OK;
+    c->parity = (p + 1u) % c->numSets;
+    return ReduceBehindVoices(c, L, p, samples_to_do);
 }
 
 void *oalgpu_post_stream(oalgpu_context *c) { return c ? static_cast<void*>(c->postStream) : nullptr; }
@@ -672,7 +836,8 @@ int oalgpu_post_process_overlapped(oalgpu_context *c, uint32_t samples_to_do, in
         // (a limiter is the update's last launch instead: evPostDone is recorded behind it)
         hipEvent_t ev = c->reduceHeld ? c->evReduceDone[c->heldParity] : ((c->timing || c->limOn) ? nullptr : c->evPostDone);
         c->lastPostEvent = (ev && !c->limOn) ? ev : c->evPostDone;
-        if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, ev)) return rc;
+        if(c->reduceHeld && c->silentPost) { if(int rc = ReduceShiftSilent(c, c->postStream, samples_to_do, ev)) return rc; }
+        else if(int rc = PostDirectHrtfFused(c, c->postStream, samples_to_do, ev)) return rc;
         postDoneBound = ev != nullptr && !c->limOn;
         if(int rc = RunLimiter(c, c->postStream, samples_to_do)) return rc;
     }

@@ -107,6 +107,7 @@ int oalgpu_context_attach(oalgpu_context *d, oalgpu_context *a, const int32_t *l
     a->attachMap.assign(line_map, line_map + srcLines);
     a->attachedTo = d;
     d->attached.push_back(a);
+    d->dryWriter = true;                    // (sticky: the merge writes the device context's dry lines)
     if(int rc = RebuildMergeTable(d))
     {
         Unlink(a);

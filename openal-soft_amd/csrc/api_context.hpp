@@ -109,13 +109,24 @@ struct oalgpu_context {
     // update k+1 (main stream) overlaps the bus reduction and the post-process of update k
     // (post stream).  The per-workgroup partial buses are double-buffered for that.
     hipStream_t postStream{nullptr};
-    hipEvent_t evVoiceDone[2]{nullptr, nullptr}, evReduceDone[2]{nullptr, nullptr}, evPostDone{nullptr};
-    uint32_t parity{0};
+    // (contexts whose voice launch may span several updates, see pendingMix, cycle through kPartSets sets: two launches in flight)
+    static constexpr uint32_t kPartSets = 2u * kSpanMax;
+    hipEvent_t evVoiceDone[2]{nullptr, nullptr}, evReduceDone[kPartSets]{}, evPostDone{nullptr};
+    uint32_t parity{0};                     // the set of partial buses the next update's sums go into
+    uint32_t numSets{2};
+    uint32_t voiceLaunches{0};              // evVoiceDone alternates per LAUNCH
+    hipEvent_t lastVoiceEvent{nullptr};     // bound to the voice launch submitted last (null: none yet)
     bool postPending{false};
     // A pipelined oalgpu_mix_update is SUBMITTED one library call late: if that next call is oalgpu_param_block_apply, the block's
     // records are installed by the update's own voice kernel -- every wavefront applies the records of the voices it has just
     // mixed, in its epilogue -- and neither ApplyParamsKernel nor its two dispatch gaps stand between two voice kernels.
-    struct { bool active{false}; uint32_t samples{0}; int post{0}; } pendingMix;
+    // Where the voice kernel has a bounded-run form (Wave16HasSpan) the deferred updates form a short queue: an update whose block
+    // has been handed over waits for the next one while the main stream is busy (or while fewer than launchSpan wait), and ONE
+    // launch then mixes them all, update by update (RunMixSpan).  Anything that flushes today submits the whole queue.
+    struct PendingUpdate { uint32_t samples{0}; int post{0}; oalgpu_param_block *behind{nullptr}; };    // behind: installed after its voices
+    struct { uint32_t count{0}; PendingUpdate u[kSpanMax]; bool active() const { return count != 0; } } pendingMix;
+    uint64_t spanCounts[kSpanMax]{}, silentPosts{0};   // oalgpu_context_launch_stats
+    uint32_t launchSpan{0};                 // oalgpu_context_set_launch_span: 0 automatic, 1 never, 2 .. kSpanMax exactly that many
     // the pipelined host boundary (oalgpu_voice_move_async / oalgpu_read_output_async): pinned ring slots
     static constexpr uint32_t kIoSlots = 4;
     oalgpu_voice_move *panHost[kIoSlots]{};
@@ -149,17 +160,20 @@ struct oalgpu_context {
     // are ONE launch (LaunchReducePostFused).  fuseReduce: this update's reduction was held back for it (oalgpu_mix_voices_overlapped
     // -> oalgpu_post_process_overlapped); reducedEpoch: what the launch's counter of reduction workgroups reads when they are through.
     bool fuseReduce{false}, reduceHeld{false};
+    // silentPost: the held reduction of this update also does what is left of the post-process of silent dry lines (api.hip:
+    // ReduceShiftSilent); dryWriter (sticky): something other than the reduction's zero fill may have written the dry lines
+    bool silentPost{false}, dryWriter{false};
     DeviceLayout heldL{};
     uint32_t heldParity{0};
     DevBuf<uint32_t> reducedCount;
     uint32_t reducedEpoch{0};
     hipEvent_t lastPostEvent{nullptr};      // what JoinPost waits for: evPostDone, or the fused launch's own event
     uint64_t updatesSubmitted{0}, updatesKnownDone{0};
-    uint64_t reduceUpdate[2]{0, 0}, panUpdate[kIoSlots]{}, outUpdate[kIoSlots]{};
+    uint64_t reduceUpdate[kPartSets]{}, panUpdate[kIoSlots]{}, outUpdate[kIoSlots]{};
     uint32_t *outFlags{nullptr};
     DevBuf<uint32_t> outArrived;
-    float *partHrtfBuf[2]{nullptr, nullptr};
-    float *partLinesBuf[2]{nullptr, nullptr};
+    float *partHrtfBuf[kPartSets]{};
+    float *partLinesBuf[kPartSets]{};
     bool timing{false}, timed{false};
     DeviceLayout L{};
     HrtfStoreDev hrtfDev{};
@@ -183,7 +197,7 @@ struct oalgpu_context {
     DevBuf<VoiceCtl> ctl;
     DevBuf<float> prev, hrtfOld, hrtfTgt, hist, gainCur, gainTgt, sendCur, sendTgt;
     DevBuf<BiquadSlot> dfilt, sfilt;
-    DevBuf<float> partLines, partLines2, partHrtf, partHrtf2, bus, streams;
+    DevBuf<float> partLines, partLines2, partHrtf, partHrtf2, partHrtfMore, bus, streams;
     DevBuf<uint32_t> lineGains;
     DevBuf<AmbiScaleState> ambi;
     DevBuf<NfcState> nfc;
@@ -371,8 +385,9 @@ struct oalgpu_context {
         if(evStart) (void)hipEventDestroy(evStart);
         if(evVoice) (void)hipEventDestroy(evVoice);
         if(evEnd) (void)hipEventDestroy(evEnd);
-        for(hipEvent_t e : {evVoiceDone[0], evVoiceDone[1], evReduceDone[0], evReduceDone[1], evPostDone})
+        for(hipEvent_t e : {evVoiceDone[0], evVoiceDone[1], evPostDone})
             if(e) (void)hipEventDestroy(e);
+        for(hipEvent_t e : evReduceDone) if(e) (void)hipEventDestroy(e);
         if(postStream) (void)hipStreamDestroy(postStream);
         if(stream && ownStream) (void)hipStreamDestroy(stream);
     }
@@ -391,6 +406,7 @@ struct oalgpu_param_block {
                                                             // near-field context; null otherwise), installed with the records
     std::vector<std::pair<uint32_t, uint32_t>> cbSteps;     // (voice, mStep) of the callback voices in the block
     oalgpu_context *heldBy{nullptr};                        // a resident context that keeps the block for its next update (res.pendingBlock)
+    oalgpu_context *queuedBy{nullptr};                      // a context whose deferred updates wait with the block between them (pendingMix)
 };
 
 // The one exchange of a sharded update: the bus block [dry + real lines | wet buses |
@@ -409,7 +425,8 @@ struct BusTransport {
 namespace oalgpu { extern thread_local std::string gLastError; }
 
 // ---- shared between the translation units (definitions: api.hip unless noted) ----
-int FlushPendingMix(oalgpu_context *c, struct oalgpu_param_block *next = nullptr);
+int FlushPendingMix(oalgpu_context *c);
+int DeferBlockBehindPending(oalgpu_context *c, struct oalgpu_param_block *b);   // oalgpu_param_block_apply on a context with deferred updates
 int UseCtx(oalgpu_context *c);
 // the update's pieces that other units launch: a context's voices and reduction on its main stream (oalgpu_mix_voices; what a
 // device context does for each attached context), the carried accumulator a reduction adds, the one-launch HRTF post-process

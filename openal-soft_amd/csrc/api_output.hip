@@ -236,6 +236,7 @@ int oalgpu_bus_device_ptr(oalgpu_context *c, void **ptr, size_t *nfloats, void *
     if(int rc = BeginSetter(c, "oalgpu_bus_device_ptr")) return rc;
     if(!ptr || !nfloats) return Fail(OALGPU_ERR_INVALID, "null argument");
     *ptr = c->L.bus;
+    c->dryWriter = true;                    // (the caller may write the lines: the context keeps its whole post-process from here on)
     *nfloats = BusFloats(c->L);
     if(hip_stream)      // the pipelined path produces the bus on the post stream, the serial entry points on the main one
         *hip_stream = (c->useWave && c->ownStream && !c->serialOnly && c->postStream) ? c->postStream : c->stream;

@@ -76,7 +76,7 @@ bool ResidentWanted(const oalgpu_context *c, int post_process)
 {
     const auto &R = c->res;
     return R.enabled && !R.failed && WaveKernelHasResident(c->L) && post_process && c->hrtfLoaded && c->directSet && !c->timing && c->cbVoices.empty()
-        && c->initPending.empty() && c->carryAccum && !c->comm && !c->pendingMix.active && c->useWave && c->ownStream && !c->serialOnly
+        && c->initPending.empty() && c->carryAccum && !c->comm && !c->pendingMix.active() && c->useWave && c->ownStream && !c->serialOnly
         && c->L.numReal >= 2 && c->L.numSlots == 0 && c->attached.empty();
 }
 

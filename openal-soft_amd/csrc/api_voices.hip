@@ -359,10 +359,11 @@ int oalgpu_param_block_apply(oalgpu_context *c, oalgpu_param_block *b)
         return OALGPU_OK;
     }
     // (a block with NFC records goes the launched way: no voice kernel installs those)
-    if(c->pendingMix.active && b->mapVoices == c->L.numVoices && WaveKernelAppliesRecords(c->L) && c->initPending.empty() && !b->nfc.p)
+    if(c->pendingMix.active() && !c->pendingMix.u[c->pendingMix.count - 1u].behind && b->mapVoices == c->L.numVoices && WaveKernelAppliesRecords(c->L)
+        && c->initPending.empty() && !b->nfc.p)
     {   // the update submitted last has not been launched yet: its voice kernel installs this block (see pendingMix)
         if(int rc = UseDevice(c->desc.device)) return rc;
-        if(int rc = FlushPendingMix(c, b)) return rc;
+        if(int rc = DeferBlockBehindPending(c, b)) return rc;
     }
     else
     {
@@ -382,6 +383,7 @@ void oalgpu_param_block_destroy(oalgpu_param_block *b)
     (void)UseDevice(b->device);                 // (resident voice kernels leave: freeing device memory waits for the device)
     // a context that still holds the block for its next resident update applies it now, while it exists
     if(b->heldBy && b->heldBy->res.pendingBlock == b) (void)FlushResidentBlock(b->heldBy);
+    if(b->queuedBy) (void)FlushPendingMix(b->queuedBy);      // (deferred updates that wait with the block between them go now)
     delete b;
 }
 

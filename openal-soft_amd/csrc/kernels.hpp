@@ -474,6 +474,13 @@ hipError_t LaunchVoiceMix(hipStream_t s, bool exact, const DeviceLayout &L, uint
 // the buffer the fused post-process left it in; null: none
 void LaunchBusReduce(hipStream_t s, const DeviceLayout &L, uint32_t samplesToDo, const float *carry, bool besideVoiceKernel = false,
     hipEvent_t evDone = nullptr);
+// Reduction and post-process of an HRTF update whose dry lines have no writer, in one launch of the post-stream shape: the
+// accumulator's columns summed as LaunchBusReduce sums them, then output lines (also into the host's ring slot: hostOut, hostFlag,
+// hostSeq, outArrived / outTarget as for LaunchPostDirectHrtfFused; BusReduceShiftGroups workgroups count in) and the shifted
+// accumulator into carryOut -- 1152 x 2 floats that `carry` does not point into
+uint32_t BusReduceShiftGroups();
+void LaunchBusReduceShift(hipStream_t s, const DeviceLayout &L, const float *carry, float *carryOut, float *left, float *right, uint32_t n,
+    hipEvent_t evDone, float *hostOut, uint32_t *hostFlag, uint32_t hostSeq, uint32_t *outArrived, uint32_t outTarget);
 
 // ---- launchers (voice_wave.hip): the FAST HRTF hot path, one wavefront per voice ----
 void LaunchSetAmbiScale(hipStream_t s, const DeviceLayout &L, uint32_t voice, const AmbiScaleState &st);
@@ -522,6 +529,15 @@ uint32_t Wave16Groups(const DeviceLayout &L);
 const char *Wave16KernelName(const DeviceLayout &L);
 hipError_t LaunchVoiceWave16(hipStream_t s, const DeviceLayout &L, uint32_t samplesToDo, const WaveProf *prof, hipEvent_t evStart, hipEvent_t evStop,
     const ParamRecord *nextRecs, const int32_t *nextMap, const float *nextRows);
+// one launch over `count` (1 .. kSpanMax) consecutive updates of a context without sends: update i mixes samples[i] frames, installs the
+// block recs[i] / map[i] / rows[i] behind its voices (map null: none) and leaves its partial buses in part[i]
+constexpr uint32_t kSpanMax = 4;
+struct SpanUpdates {
+    uint32_t count, samples[kSpanMax];
+    const ParamRecord *recs[kSpanMax]; const int32_t *map[kSpanMax]; const float *rows[kSpanMax]; float *part[kSpanMax];
+};
+bool Wave16HasSpan(const DeviceLayout &L);
+hipError_t LaunchVoiceWave16Span(hipStream_t s, const DeviceLayout &L, const SpanUpdates &span, hipEvent_t evStop);
 hipError_t LaunchVoiceWaveResident(hipStream_t s, const DeviceLayout &L, const ResidentArgs &args, hipEvent_t evStart, hipEvent_t evStop);
 int WaveResidentGroupsPerCu(const DeviceLayout &L);
 hipError_t LaunchVoiceWave16Resident(hipStream_t s, const DeviceLayout &L, const ResidentArgs &args, hipEvent_t evStart, hipEvent_t evStop);

@@ -1184,7 +1184,113 @@ __global__ void __launch_bounds__(kReduceWaves * 64) __attribute__((amdgpu_num_v
     }
 }
 
+// The reduction AND the post-process of an HRTF update whose dry lines have no writer (no effect slots, no attached context, no
+// collective: the voices mix into the accumulator only, and the splitters have never seen anything but the reduction's zero
+// fill).  MixDirectHrtf then adds nothing to the accumulator -- the decoder's FIR over zero lines is +0 -- so what is left of
+// PostFusedBlock (post_wave.hip) is its last block: s = accumulator + 0, the two output lines = zero fill + s, the shift of
+// hrtfbase.h:127-132.  One workgroup per 64 accumulator floats (32 frames, both ears): BusReduceKernel<4>'s sums in its order,
+// then those additions per element -- the same numbers as the two launches.  The shifted value of a column lands where another
+// workgroup reads ITS carry: `carryOut` is never the buffer `carry` points into (the host alternates between two).
+struct ReduceShiftArgs {
+    const float *carry; float *carryOut, *left, *right; uint32_t n;
+    float *hostOut; uint32_t *hostFlag; uint32_t hostSeq; uint32_t *outArrived; uint32_t outTarget;
+};
+__global__ void __launch_bounds__(4 * 64) __attribute__((amdgpu_num_vgpr(48))) BusReduceShiftKernel(DeviceLayout L, ReduceShiftArgs A)
+{
+    __shared__ float slice[4][64];
+    __builtin_amdgcn_s_setprio(3);
+    const uint32_t wave0 = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t idx = blockIdx.x * 64u + lane;                  // float of the accumulator: frame idx / 2, ear idx & 1
+    constexpr uint32_t stride = uint32_t(kLine + kHrirLen) * 2u;
+    typedef const __attribute__((address_space(1))) float *gfloatp;
+    typedef const __attribute__((address_space(1))) char *gcharp;
+    gfloatp base;
+    {
+        const uint64_t b = reinterpret_cast<uint64_t>(L.partHrtf);
+        const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b)), hi = __builtin_amdgcn_readfirstlane(uint32_t(b >> 32));
+        base = reinterpret_cast<gfloatp>((uint64_t{hi} << 32) | lo);
+    }
+    const uint32_t ngroups = L.numGroups;
+    const uint32_t per = (ngroups + kReduceSegs - 1) / kReduceSegs;
+    const uint32_t sb = stride * 4u;
+    uint32_t gA[4], gE[4], oo[4];
+    float sum[4];
+    uint32_t common = per;
+#pragma unroll
+    for(int q = 0; q < 4; ++q)
+    {
+        const uint32_t seg = wave0 + 4u * uint32_t(q);
+        gA[q] = seg * per < ngroups ? seg * per : ngroups;
+        gE[q] = (gA[q] + per < ngroups) ? gA[q] + per : ngroups;
+        oo[q] = (idx + gA[q] * stride) * 4u;
+        sum[q] = 0.0f;
+        common = (gE[q] - gA[q]) < common ? gE[q] - gA[q] : common;
+    }
+#pragma unroll 1
+    for(uint32_t j = 0; j + 8 <= common; j += 8)
+    {
+        float v[4][8];
+#pragma unroll
+        for(int q = 0; q < 4; ++q)
+#pragma unroll
+            for(int k = 0; k < 8; ++k) v[q][k] = OALGPU_PARTIAL_LOAD(reinterpret_cast<gfloatp>(reinterpret_cast<gcharp>(base) + (oo[q] + uint32_t(k) * sb)));
+#pragma unroll
+        for(int q = 0; q < 4; ++q)
+        {
+#pragma unroll
+            for(int k = 0; k < 8; ++k) sum[q] = sum[q] + v[q][k];
+            oo[q] += 8u * sb; gA[q] += 8u;
+        }
+    }
+#pragma unroll
+    for(int q = 0; q < 4; ++q)
+        for(; gA[q] < gE[q]; ++gA[q]) { sum[q] = sum[q] + *reinterpret_cast<gfloatp>(reinterpret_cast<gcharp>(base) + oo[q]); oo[q] += sb; }
+    float t = A.carry ? A.carry[idx] : 0.0f;
+#pragma unroll
+    for(int q = 0; q < 4; ++q)
+    {
+        slice[wave0][lane] = sum[q];
+        __syncthreads();
+        if(wave0 == 0) { t = t + slice[0][lane]; t = t + slice[1][lane]; t = t + slice[2][lane]; t = t + slice[3][lane]; }
+        __syncthreads();
+    }
+    if(wave0 != 0) return;
+    const uint32_t o = idx >> 1, ear = idx & 1u, n = A.n;
+    const float s = t + 0.0f;                                      // accumulator + the channels' sum
+    if(o < uint32_t(kLine))
+    {
+        const float out = (o < n) ? 0.0f + s : 0.0f;               // the line's zero fill + s
+        (ear ? A.right : A.left)[o] = out;
+        if(A.hostOut) A.hostOut[ear * uint32_t(kLine) + o] = out;
+    }
+    // hrtfbase.h:127-132: frames [n, n + 128) move to the front, the following n frames are cleared, anything beyond stays
+    if(o >= n && o < n + uint32_t(kHrirLen)) A.carryOut[2u * (o - n) + ear] = s;
+    if(o >= uint32_t(kHrirLen)) A.carryOut[idx] = (o < uint32_t(kHrirLen) + n) ? 0.0f : s;
+    if(A.hostOut)
+    {   // the slot's sequence number goes out behind the last workgroup's lines (PostFusedBlock's hand-over)
+        __threadfence_system();
+        if(lane == 0)
+        {
+            const uint32_t arrived = __hip_atomic_fetch_add(A.outArrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            if(arrived + 1u == A.outTarget)
+            {
+                __threadfence_system();
+                __hip_atomic_store(A.hostFlag, A.hostSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
 } // namespace
+
+uint32_t BusReduceShiftGroups() { return uint32_t(kLine + kHrirLen) * 2u / 64u; }
+void LaunchBusReduceShift(hipStream_t s, const DeviceLayout &L, const float *carry, float *carryOut, float *left, float *right, uint32_t n,
+    hipEvent_t evDone, float *hostOut, uint32_t *hostFlag, uint32_t hostSeq, uint32_t *outArrived, uint32_t outTarget)
+{
+    static_assert((kLine + kHrirLen) * 2 % 64 == 0, "whole workgroups");
+    const ReduceShiftArgs A{carry, carryOut, left, right, n, hostOut, hostFlag, hostSeq, outArrived, outTarget};
+    hipExtLaunchKernelGGL(BusReduceShiftKernel, dim3(BusReduceShiftGroups()), dim3(4 * 64), 0, s, nullptr, evDone, 0u, L, A);
+}
 
 hipError_t LaunchVoiceMix(hipStream_t s, bool exact, const DeviceLayout &L, uint32_t samplesToDo, bool carryAccum)
 {

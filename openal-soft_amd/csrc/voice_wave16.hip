@@ -225,6 +225,13 @@ struct Next16 { const ParamRecord *recs; const int32_t *map; const float *rows; 
 // send's own filter pair when that is active -- leaves as ONE 4 KB stream row per voice and send with the resolved gains of the slot's
 // wet lines (voice_wave.hip's StoreRowBlock); StreamRowsMixKernel, launched behind this kernel, turns a workgroup's rows into its
 // partial wet lines.  The HRTF path keeps its 110 registers: no line accumulator lives beside the FIR.
+// the bounded run's arguments (SpanUpdates) as the kernel takes them: scalars by name -- an array in the argument block that is
+// indexed by the turn becomes a stack copy of it
+static_assert(kSpanMax == 4, "the bounded run picks its turn's arguments out of four");
+struct Span16 {
+    uint32_t count, n0, n1, n2, n3;
+    const ParamRecord *r0, *r1, *r2, *r3; const int32_t *m0, *m1, *m2, *m3; const float *w0, *w1, *w2, *w3; float *p0, *p1, *p2, *p3;
+};
 struct W16Sends {
     BiquadSlot *sfilt; const float *sendTgt; float *sendCur; float *streams; uint32_t *lineGains;
     uint32_t numSends, wetCh, lineStride, spv;
@@ -236,9 +243,15 @@ struct W16Sends {
 // RES: the resident launch (OALGPU_CTX_RESIDENT; the protocol: kernels.hpp ResidentDoor, voice_wave.hip) -- the kernel's body is one
 // UPDATE of a loop that ends when the host says so; everything a launch does per update it does per turn of that loop, in the same order
 // with the same operations: the bits are those of one launch per update (tests/test_gpu_resident.py).
-template<bool PROF, int WAVES, bool SENDS = false, bool RES = false>
-__global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Kernel(WaveArgsHrtf L, uint32_t samplesToDo, Next16 next, WaveProf prof, W16Sends S)
+// SPAN: the bounded run (the deferred updates a host has already handed over, OALGPU_CTX_APPLY_IN_VOICE_KERNEL): the same loop without the
+// door -- nothing polls and nothing waits; turn i is the launched body of update i with ITS length, block and partial set, then the
+// barrier and the scalar-cache invalidate the resident loop has between two updates (tests/test_gpu_launch_span.py)
+template<bool PROF, int WAVES, bool SENDS = false, bool RES = false, bool SPAN = false>
+__global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Kernel(WaveArgsHrtf L, uint32_t samplesToDo, Next16 next, WaveProf prof,
+    std::conditional_t<SPAN, Span16, W16Sends> S)
 {
+    static_assert(!(SPAN && (RES || SENDS || PROF)), "the bounded run is a product form without sends");
+    constexpr bool LOOP = RES || SPAN;
     unsigned long long tEntry = 0;
     if constexpr (PROF) tEntry = __builtin_readcyclecounter();
     constexpr uint32_t kW16Waves = uint32_t(WAVES), kW16Threads = uint32_t(WAVES) * 64u;
@@ -262,6 +275,7 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
 
     // ---- RES: this launch's turn of the update loop (one pass through the kernel's body otherwise) ----
     uint32_t upd = 0u, updBase = 0u;
+    uint32_t turn = 0u;                         // SPAN: the update of this launch the loop is at
     if constexpr (RES)
     {
         const ResidentArgs &RA = next.res;
@@ -278,8 +292,30 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
     // RES: thread and lane index are re-derived per update behind an opaque move: what the body computes from them then is a few VALU
     // per update, not a set of loop invariants kept in registers across the resampler and the FIR, whose peaks decide the register count
     uint32_t tU = threadIdx.x;
-    if constexpr (RES) { asm volatile("" : "+v"(tU)); lane = tU & 63u; }
+    if constexpr (LOOP) { asm volatile("" : "+v"(tU)); lane = tU & 63u; }
     const uint32_t t = tU;
+    if constexpr (SPAN)
+    {   // the turn's own arguments go through sm.res, as the resident loop's do: its length is read back here, its block and its
+        // partial set where they are used.  (Every wavefront's lane 0 stores the same words and reads them behind its OWN stores:
+        // no barrier; the turn before ended with one.)
+        const uint32_t i = turn;
+        auto stash = [&](uint32_t n, const ParamRecord *recs, const int32_t *map, const float *rows, float *part)
+        {
+            if(lane != 0) return;
+            const uint64_t r = reinterpret_cast<uint64_t>(recs), m = reinterpret_cast<uint64_t>(map), w = reinterpret_cast<uint64_t>(rows),
+                p = reinterpret_cast<uint64_t>(part);
+            sm.res[1] = n;
+            sm.res[2] = uint32_t(r); sm.res[3] = uint32_t(r >> 32); sm.res[4] = uint32_t(m); sm.res[5] = uint32_t(m >> 32);
+            sm.res[8] = uint32_t(w); sm.res[9] = uint32_t(w >> 32); sm.res[10] = uint32_t(p); sm.res[11] = uint32_t(p >> 32);
+        };
+        // (a branch per turn, each with its own few scalar loads: a select among all four turns' arguments holds them all at once)
+        if(i == 0u) stash(S.n0, S.r0, S.m0, S.w0, S.p0);
+        else if(i == 1u) stash(S.n1, S.r1, S.m1, S.w1, S.p1);
+        else if(i == 2u) stash(S.n2, S.r2, S.m2, S.w2, S.p2);
+        else stash(S.n3, S.r3, S.m3, S.w3, S.p3);
+        WaveSync();
+        N = __builtin_amdgcn_readfirstlane(sm.res[1]);
+    }
     if constexpr (RES)
     {
         const ResidentArgs &RA = next.res;
@@ -385,7 +421,8 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
     // (RES: the rows staged by an earlier update of this launch are still there unless the key voice's resampler changed)
     bool stageRows = true;
     if constexpr (RES) { if(upd != updBase) stageRows = !(eligK && sm.tabKey == offK * 8u + uint32_t(kK) && sm.tabM == mK); }
-    if constexpr (RES) __syncthreads();         // (everybody has compared before thread 0 rewrites the key)
+    if constexpr (SPAN) { if(turn != 0u) stageRows = !(eligK && sm.tabKey == offK * 8u + uint32_t(kK) && sm.tabM == mK); }
+    if constexpr (LOOP) __syncthreads();        // (everybody has compared before thread 0 rewrites the key)
     if(eligK && stageRows)
     {
         typedef const __attribute__((address_space(1))) void *gvoidp;
@@ -956,14 +993,24 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
     // of the dump's barrier: the install is a chain of dependent round trips (map entry -> record -> stores), and all but the
     // workgroup's last wavefront spend it waiting for that one anyway.  The voice's state was written back by this very wavefront,
     // in program order.
-    if(!RES && next.map && haveVoice)
+    const ParamRecord *nextRecs = next.recs;
+    const int32_t *nextMap = next.map;
+    const float *nextRows = next.rows;
+    if constexpr (SPAN)
+    {
+        auto word = [&](int k) { return uint64_t{uint32_t(__builtin_amdgcn_readfirstlane(sm.res[k]))}; };
+        nextRecs = reinterpret_cast<const ParamRecord*>((word(3) << 32) | word(2));
+        nextMap = reinterpret_cast<const int32_t*>((word(5) << 32) | word(4));
+        nextRows = reinterpret_cast<const float*>((word(9) << 32) | word(8));
+    }
+    if(!RES && nextMap && haveVoice)
     {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if(next.rows && irStride <= 64u) InstallPair(L, next.map, next.recs, next.rows, v, v, false, lane);
+        if(nextRows && irStride <= 64u) InstallPair(L, nextMap, nextRecs, nextRows, v, v, false, lane);
         else
         {
-            const int32_t ri = __builtin_amdgcn_readfirstlane(next.map[v]);
-            if(ri >= 0) ApplyNextRecord(L, next.recs[ri], lane);
+            const int32_t ri = __builtin_amdgcn_readfirstlane(nextMap[v]);
+            if(ri >= 0) ApplyNextRecord(L, nextRecs[ri], lane);
         }
     }
     stamp(5);
@@ -983,7 +1030,12 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
             for(int r = 0; r < 4; ++r) dump[17u * (64u + jc) + 4u * q4 + uint32_t(r)] = f2{accM[0][4][r], accM[1][4][r]};
         }
         __syncthreads();
-        f2 *ph = reinterpret_cast<f2*>(L.partHrtf) + size_t{group} * (kLine + kHrirLen);
+        float *partHrtf = L.partHrtf;
+        if constexpr (SPAN)
+        {
+            partHrtf = reinterpret_cast<float*>((uint64_t{uint32_t(__builtin_amdgcn_readfirstlane(sm.res[11]))} << 32) | uint32_t(__builtin_amdgcn_readfirstlane(sm.res[10])));
+        }
+        f2 *ph = reinterpret_cast<f2*>(partHrtf) + size_t{group} * (kLine + kHrirLen);
         if constexpr (RES)      // the update's set of partial buses
             ph = reinterpret_cast<f2*>(next.res.partBase + size_t{upd % kResidentSets} * next.res.setStride) + size_t{group} * (kLine + kHrirLen);
         for(uint32_t k = t; k < uint32_t(kLine + kHrirLen); k += uint32_t(kW16Threads))
@@ -1001,7 +1053,17 @@ __global__ void OALGPU_SINGLE_DS_OPS __launch_bounds__(WAVES * 64) VoiceWave16Ke
         }
     }
     stamp(6);
-    if constexpr (!RES) break;
+    if constexpr (SPAN)
+    {   // on to the launch's next update: what it reads through the scalar cache -- the voices' control lines -- was written with
+        // vector stores, by this wavefront and (the key voice's head) by the key voice's: in L2 before the barrier, the scalar
+        // cache forgets behind it (the resident loop's step between two updates)
+        if(++turn == S.count) break;
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        __builtin_amdgcn_s_dcache_inv();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    else if constexpr (!RES) break;
     else
     {   // the workgroup's partial is where the reduction will read it (written through, every thread's stores acknowledged)
         // before the workgroup counts as arrived for this update; then on to the next one
@@ -1068,6 +1130,23 @@ hipError_t LaunchVoiceWave16(hipStream_t s, const DeviceLayout &L, uint32_t samp
         if(L.wave16 == 16u) OALGPU_W16_LAUNCH(false, 16, false, none); else if(L.wave16 == 8u) OALGPU_W16_LAUNCH(false, 8, false, none); else OALGPU_W16_LAUNCH(false, 4, false, none);
     }
 #undef OALGPU_W16_LAUNCH
+    return hipGetLastError();
+}
+
+// the bounded run: ONE launch over span.count consecutive updates (contexts without sends; span.part[i]: update i's partial buses)
+bool Wave16HasSpan(const DeviceLayout &L) { return L.wave16 != 0u && L.numSends == 0u && Wave16Applies(L); }
+hipError_t LaunchVoiceWave16Span(hipStream_t s, const DeviceLayout &L, const SpanUpdates &span, hipEvent_t evStop)
+{
+    if(span.count == 0u || span.count > kSpanMax) return hipErrorInvalidValue;
+    const SpanUpdates &u = span;
+    const Span16 S{u.count, u.samples[0], u.samples[1], u.samples[2], u.samples[3], u.recs[0], u.recs[1], u.recs[2], u.recs[3],
+        u.map[0], u.map[1], u.map[2], u.map[3], u.rows[0], u.rows[1], u.rows[2], u.rows[3], u.part[0], u.part[1], u.part[2], u.part[3]};
+    const Next16 next{nullptr, nullptr, nullptr, ResidentArgs{}};
+    const WaveProf none{nullptr, 0u};
+    const dim3 grid(Wave16Groups(L)), block(L.wave16 * 64u);
+#define OALGPU_W16_SPAN(W) hipExtLaunchKernelGGL((VoiceWave16Kernel<false, W, false, false, true>), grid, block, 0, s, nullptr, evStop, 0u, WaveArgsHrtf{L}, 0u, next, none, S)
+    if(L.wave16 == 16u) OALGPU_W16_SPAN(16); else if(L.wave16 == 8u) OALGPU_W16_SPAN(8); else OALGPU_W16_SPAN(4);
+#undef OALGPU_W16_SPAN
     return hipGetLastError();
 }
 

@@ -86,6 +86,8 @@ CTX_RESIDENT = 64
 CTX_SLICE_LINES = 128
 CTX_WAVE_PAIRS = 256
 CTX_ROW_SLICES = 512
+CTX_SPAN_ONE = 1024
+CTX_FULL_POST = 2048
 
 
 class VoiceDesc(C.Structure):
@@ -297,6 +299,7 @@ def _load(path=LIB_PATH):
     L.oalgpu_mix_voices.argtypes = [C.c_void_p, C.c_uint32]
     L.oalgpu_post_process.argtypes = [C.c_void_p, C.c_uint32]
     L.oalgpu_set_carry_accum.argtypes = [C.c_void_p, C.c_int]
+    L.oalgpu_context_set_launch_span.argtypes = [C.c_void_p, C.c_uint32]
     L.oalgpu_sync.argtypes = [C.c_void_p]
     L.oalgpu_read_dry.argtypes = [C.c_void_p, f32p]
     L.oalgpu_read_wet.argtypes = [C.c_void_p, C.c_uint32, f32p]
@@ -898,6 +901,17 @@ class Scene:
 
     def set_carry_accum(self, enable):
         check(lib.oalgpu_set_carry_accum(self.h, 1 if enable else 0))
+
+    def set_launch_span(self, n):
+        """deferred updates per voice launch: 0 automatic, 1 never more than one, 2..4 exactly that many"""
+        check(lib.oalgpu_context_set_launch_span(self.h, n), "oalgpu_context_set_launch_span")
+
+    def launch_stats(self):
+        """-> ([voice launches that covered 1, 2, 3, 4 updates], updates post-processed by the one reduce-and-shift launch)"""
+        spans, silent = (C.c_uint64 * 4)(), C.c_uint64()
+        lib.oalgpu_context_launch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        check(lib.oalgpu_context_launch_stats(self.h, spans, C.byref(silent)), "oalgpu_context_launch_stats")
+        return list(spans), silent.value
 
     def set_start_delay(self, voice, samples):
         lib.oalgpu_voice_set_start_delay.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
