@@ -640,6 +640,11 @@ int oalgpu_context_set_launch_span(oalgpu_context *ctx, uint32_t n);
  * spans[i] = voice launches that covered i + 1 updates; *silent_posts = updates whose reduction and post-process were the one
  * launch of a context whose dry lines have no writer (see OALGPU_CTX_FULL_POST).  Either pointer may be NULL. */
 int oalgpu_context_launch_stats(oalgpu_context *ctx, uint64_t spans[4], uint64_t *silent_posts);
+/* *guard_queries = voice launches that had to ask the runtime whether the newest reduction that read a partial-bus set they write
+ * had ended (one query per launch at most, however many updates it covers; none where the host already knows, as after
+ * oalgpu_sync); *main_stream_guards = those of them that were told no and put a stream wait into the main stream in front of
+ * the voice kernel.  Either pointer may be NULL.  Nothing is flushed. */
+int oalgpu_context_guard_stats(oalgpu_context *ctx, uint64_t *main_stream_guards, uint64_t *guard_queries);
 int oalgpu_sync(oalgpu_context *ctx);
 /* OALGPU_CTX_RESIDENT: what the mode has done so far.  timed_*: launches that have ended -- their own durations (HIP events
  * bound to the dispatch) and the updates they covered; timed_kernel_ms / timed_updates is the voice kernel's time per update. */

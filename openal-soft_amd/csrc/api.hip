@@ -573,6 +573,7 @@ int oalgpu_post_process(oalgpu_context *c, uint32_t samples_to_do)
 static int RunMixUpdate(oalgpu_context *c, uint32_t samples_to_do, int post_process, oalgpu_param_block *next);
 static void PlanPost(oalgpu_context *c, int post_process);
 static int GuardPartialSet(oalgpu_context *c, uint32_t p);
+static int GuardPartialSets(oalgpu_context *c, const uint32_t *sets, uint32_t count);
 static int ReduceBehindVoices(oalgpu_context *c, const DeviceLayout &L, uint32_t p, uint32_t samples_to_do);
 
 // How many deferred updates ONE voice launch of the context may cover right now (1: a launch per update).  A launch spans updates
@@ -628,6 +629,14 @@ int oalgpu_context_launch_stats(oalgpu_context *c, uint64_t spans[4], uint64_t *
     static_assert(kSpanMax == 4, "oalgpu.h says four");
     if(spans) for(uint32_t i = 0; i < kSpanMax; ++i) spans[i] = c->spanCounts[i];
     if(silent_posts) *silent_posts = c->silentPosts;
+    return OALGPU_OK;
+}
+
+int oalgpu_context_guard_stats(oalgpu_context *c, uint64_t *main_stream_guards, uint64_t *guard_queries)
+{
+    if(!c) return Fail(OALGPU_ERR_INVALID, "null argument");
+    if(main_stream_guards) *main_stream_guards = c->mainStreamGuards;
+    if(guard_queries) *guard_queries = c->guardQueries;
     return OALGPU_OK;
 }
 
@@ -718,10 +727,11 @@ static int RunMixSpan(oalgpu_context *c, const oalgpu_context::PendingUpdate *u,
     SpanUpdates span{};
     span.count = count;
     uint32_t sets[kSpanMax];
+    for(uint32_t i = 0; i < count; ++i) sets[i] = (c->parity + i) % c->numSets;
+    if(int rc = GuardPartialSets(c, sets, count)) return rc;
     for(uint32_t i = 0; i < count; ++i)
     {
-        const uint32_t p = sets[i] = (c->parity + i) % c->numSets;
-        if(int rc = GuardPartialSet(c, p)) return rc;
+        const uint32_t p = sets[i];
         const oalgpu_param_block *b = u[i].behind;
         span.samples[i] = u[i].samples;
         span.recs[i] = b ? b->recs.p : nullptr; span.map[i] = b ? b->voiceToRec.p : nullptr; span.rows[i] = b ? b->rows.p : nullptr;
@@ -747,15 +757,26 @@ static int RunMixSpan(oalgpu_context *c, const oalgpu_context::PendingUpdate *u,
 
 // in front of a voice launch that writes partial set p: the set was last read by the reduction of numSets updates ago
 // (almost always long done: then no barrier packet goes into the main queue in front of the voice kernel)
-static int GuardPartialSet(oalgpu_context *c, uint32_t p)
+static int GuardPartialSet(oalgpu_context *c, uint32_t p) { return GuardPartialSets(c, &p, 1u); }
+
+// The same in front of a voice launch that writes `count` sets, in the order of its updates: ONE query and at most ONE wait.  The
+// reductions run in order on one stream (the post stream; with the whole post chain between them as well), so the event of the
+// newest one that read any of the sets stands for them all -- four waits were four barrier packets in the main queue, each
+// taken up only when the launch before had ended (5 us apiece between two launches, profiles/span_guard).  An event found ready
+// proves every update up to its own reduced: launches to come skip the query.
+static int GuardPartialSets(oalgpu_context *c, const uint32_t *sets, uint32_t count)
 {
-    if(c->reduceUpdate[p] > c->updatesKnownDone)
+    uint32_t newest = sets[0];
+    for(uint32_t i = 1; i < count; ++i) if(c->reduceUpdate[sets[i]] > c->reduceUpdate[newest]) newest = sets[i];
+    if(c->reduceUpdate[newest] > c->updatesKnownDone)
     {
-        const hipError_t q = hipEventQuery(c->evReduceDone[p]);
-        if(q == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(c->stream, c->evReduceDone[p], 0));
-        else HIP_TRY(q);
+        hipEvent_t ev = c->evReduceDone[newest];
+        const hipError_t q = hipEventQuery(ev);
+        ++c->guardQueries;
+        if(q == hipErrorNotReady) { HIP_TRY(hipStreamWaitEvent(c->stream, ev, 0)); ++c->mainStreamGuards; }
+        else { HIP_TRY(q); c->updatesKnownDone = c->reduceUpdate[newest]; }
     }
-    c->reduceUpdate[p] = ++c->updatesSubmitted;
+    for(uint32_t i = 0; i < count; ++i) c->reduceUpdate[sets[i]] = ++c->updatesSubmitted;
     return OALGPU_OK;
 }
 

@@ -126,6 +126,7 @@ struct oalgpu_context {
     struct PendingUpdate { uint32_t samples{0}; int post{0}; oalgpu_param_block *behind{nullptr}; };    // behind: installed after its voices
     struct { uint32_t count{0}; PendingUpdate u[kSpanMax]; bool active() const { return count != 0; } } pendingMix;
     uint64_t spanCounts[kSpanMax]{}, silentPosts{0};   // oalgpu_context_launch_stats
+    uint64_t mainStreamGuards{0}, guardQueries{0};     // oalgpu_context_guard_stats
     uint32_t launchSpan{0};                 // oalgpu_context_set_launch_span: 0 automatic, 1 never, 2 .. kSpanMax exactly that many
     // the pipelined host boundary (oalgpu_voice_move_async / oalgpu_read_output_async): pinned ring slots
     static constexpr uint32_t kIoSlots = 4;

@@ -913,6 +913,13 @@ class Scene:
         check(lib.oalgpu_context_launch_stats(self.h, spans, C.byref(silent)), "oalgpu_context_launch_stats")
         return list(spans), silent.value
 
+    def guard_stats(self):
+        """-> (stream waits put into the main stream in front of voice launches, voice launches that had to query an event first)"""
+        guards, queries = C.c_uint64(), C.c_uint64()
+        lib.oalgpu_context_guard_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        check(lib.oalgpu_context_guard_stats(self.h, C.byref(guards), C.byref(queries)), "oalgpu_context_guard_stats")
+        return guards.value, queries.value
+
     def set_start_delay(self, voice, samples):
         lib.oalgpu_voice_set_start_delay.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         check(lib.oalgpu_voice_set_start_delay(self.h, voice, samples), "oalgpu_voice_set_start_delay")
