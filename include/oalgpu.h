@@ -579,9 +579,9 @@ int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_list
  * csrc/source_channel_kernels.hip), one wavefront per channel voice.  A MONO source with spatialize ON or AUTO yields what
  * oalgpu_voice_set_source_props yields for its props (`panning` does not reach a mono source: the reference hands 0 down
  * unless mPanningEnabled).
- * NOT covered: DirectChannels other than off (RealOut.ChannelIndex, RemixMap), B-Format / UHJ / Super Stereo sources
- * (CalcAmbisonicPanning: on a near-field context they keep oalgpu_voice_set_nfc), mPanningEnabled mono sources
- * (MergePannedMono, mDuplicateMono), Pairwise rendering, callback voices. */
+ * NOT covered: DirectChannels other than off (RealOut.ChannelIndex, RemixMap), UHJ / Super Stereo sources (B-Format sources
+ * are oalgpu_ambi_source's, below), mPanningEnabled mono sources (MergePannedMono, mDuplicateMono), Pairwise rendering,
+ * callback voices. */
 enum oalgpu_source_channels {           /* FmtChannels, the non-ambisonic ones */
     OALGPU_CHANNELS_MONO, OALGPU_CHANNELS_STEREO, OALGPU_CHANNELS_REAR, OALGPU_CHANNELS_QUAD,
     OALGPU_CHANNELS_X51, OALGPU_CHANNELS_X61, OALGPU_CHANNELS_X71 };
@@ -625,6 +625,78 @@ int oalgpu_nfc_adjust_host(float w1, float w0, float *coeffs);
 /* What NFCtrlFilter.adjust left in a voice (read back; waits for the context's work in flight): *has_nfc <- VoiceFlag::HasNfc,
  * coeffs[14] <- the voice's a[o][0] and b[o][1..o] in oalgpu_channel_source_nfc_host's order.  Near-field contexts only. */
 int oalgpu_voice_nfc_readback(oalgpu_context *ctx, uint32_t voice, int32_t *has_nfc, float *coeffs);
+
+/* ---- The same for B-Format sources: CalcAmbisonicPanning (alc/alu.cpp:911-1076) -------------------------------------
+ * A FmtBFormat2D / FmtBFormat3D source of order 1..4 is one voice per channel (oalgpu_buffer_channel_view,
+ * oalgpu_voice_set_ambi_scale), in the buffer's channel order: (order + 1)^2 channels for 3D, 2 order + 1 for 2D.  The route
+ * (alu.cpp:2024-2030): a B-Format source is never "mono 3D", so spatialize OFF and AUTO take CalcNonAttnVoiceParams (the
+ * source plays around the listener, distance 0), ON takes CalcAttnVoiceParams.  Then: coverage = 1 at the listener, else
+ * spread / (2 pi); without coverage channel 0 alone is panned as a point source; otherwise the source's orientation (through
+ * the listener matrix unless head-relative) becomes a rotation of every band up to the device's order (AmbiRotator,
+ * :799-888), the rotation is upsampled when the device's order exceeds the source's or a 2D source plays on a 3D device of
+ * order >= 2 (UpsampleBFormatTransform, :457-477), and channel c's line gains are ComputePanGains over row index_map[c] of
+ * that matrix under the layout's and the scaling's tables, channel 0's blended with the panned W by the coverage.  Filters,
+ * mStep and the resampler are the source's, equal in all its channel voices.  The rotator's constants are RotatorCoeffs'
+ * (:738-792) but for v of m = 0, which is Ivanic and Ruedenberg's -sqrt((l - 1) l / (2 denom)): the reference's
+ * -sqrt((l - 1) l / denom) (:774) does not give a rotation in the columns |m| <= l - 2, so on a 3D device of order >= 2 a
+ * rotated source differs from the reference there; a 2D device does not read those columns.  One kernel (AmbiParamsKernel,
+ * csrc/source_ambi_kernels.hip), one 64-lane workgroup per source.  Dry-line contexts only.
+ * NOT covered: UHJ and Super Stereo formats (FmtUHJ2 / 3 / 4, FmtSuperStereo: their decoders run ahead of the mix), Pairwise
+ * rendering (ScaleAzimuthFront3_2), HRTF contexts (their voice kernels mix only through the FIR), near-field contexts (below),
+ * callback voices. */
+enum oalgpu_ambi_layout { OALGPU_AMBI_LAYOUT_FUMA, OALGPU_AMBI_LAYOUT_ACN };                         /* AmbiLayout */
+enum oalgpu_ambi_scaling { OALGPU_AMBI_SCALING_FUMA, OALGPU_AMBI_SCALING_SN3D, OALGPU_AMBI_SCALING_N3D }; /* AmbiScaling */
+#define OALGPU_MAX_AMBI_ORDER 4         /* core/ambidefs.h:18 */
+#define OALGPU_MAX_FUMA_ORDER 3         /* what AmbiScale::FromFuMa, AmbiIndex::FromFuMa and ::FromFuMa2D reach */
+/* DeviceBase::mAmbiOrder (1..4) and m2DMixing; the dry bus's AmbiMap stays oalgpu_context_set_ambi_map's.  Waits for the
+ * context's work in flight. */
+int oalgpu_context_set_ambi_order(oalgpu_context *ctx, uint32_t order, int32_t mix_2d);
+/* One of AmbiScale::FirstOrderUp .. FourthOrder2DUp (core/ambidefs.cpp) for sources of source_order and that dimensionality:
+ * rows x OALGPU_MAX_AMBI_CHANNELS floats, rows = (source_order + 1)^2.  The caller supplies it, as the reverb's
+ * first_order_up is supplied; the library holds none of these tables (there is no fourth-order 3D one: a
+ * fourth-order 3D source is never upsampled).  May be called again; waits for the context's work in flight. */
+int oalgpu_context_set_ambi_upsampler(oalgpu_context *ctx, uint32_t source_order, int32_t is_2d, const float *matrix, uint32_t rows);
+typedef struct oalgpu_ambi_source {
+    oalgpu_source_props props;          /* as above */
+    int32_t spatialize;                 /* mSpatializeMode (oalgpu_spatialize) */
+    int32_t is_2d;                      /* FmtBFormat2D */
+    uint32_t order;                     /* mAmbiOrder, 1..4 */
+    int32_t layout, scaling;            /* mAmbiLayout (oalgpu_ambi_layout), mAmbiScaling (oalgpu_ambi_scaling) */
+    float orient_at[3], orient_up[3];   /* OrientAt, OrientUp */
+    uint32_t voices[OALGPU_MAX_AMBI_CHANNELS];     /* the channel voices, in the buffer's channel order; OALGPU_NO_VOICE: none */
+} oalgpu_ambi_source;
+/* The synchronous form, with oalgpu_voice_set_channel_sources' semantics.  Refuses, with nothing changed, what that call
+ * refuses, and with OALGPU_ERR_INVALID: an HRTF context; a context that has not been told its order
+ * (oalgpu_context_set_ambi_order); spatialize, order, layout or scaling out of range; FuMa layout or scaling above
+ * OALGPU_MAX_FUMA_ORDER; a source that needs an upsampler the context has not been given; a context with near-field control
+ * (oalgpu_context_set_nfc).  There CalcAmbisonicPanning (:919-941) adjusts channel 0's NFCtrlFilter to the source's w0, or every
+ * channel's to 0 for a source at the listener, and otherwise leaves the other channels what Voice::prepare gave them --
+ * NfcFilter::init(w1), the pass-through b = a(w1), a0 = 1, which is NOT what adjust(0) leaves (b = 0, a0 = mBaseGain;
+ * core/filters/nfc.cpp:56-83) and which no voice of this library holds by itself: B-Format voices on a near-field context keep
+ * the per-voice oalgpu_voice_set_nfc. */
+int oalgpu_voice_set_ambi_sources(oalgpu_context *ctx, const oalgpu_ambi_source *sources, size_t count);
+/* The same into an ordinary oalgpu_param_block, as oalgpu_param_block_create_from_sources. */
+int oalgpu_param_block_create_from_ambi_sources(oalgpu_context *ctx, const oalgpu_ambi_source *sources, size_t count,
+    oalgpu_param_block **out);
+/* The device side of a context as the host form is told of it: [source order - 1][is_2d] upsamplers (NULL: not given). */
+typedef struct oalgpu_ambi_device {
+    uint32_t order;                     /* DeviceBase::mAmbiOrder */
+    int32_t mix_2d;                     /* DeviceBase::m2DMixing */
+    const float *upsampler[OALGPU_MAX_AMBI_ORDER][2];
+} oalgpu_ambi_device;
+/* The same arithmetic compiled for the host, with oalgpu_source_params_host's arguments (desc->hrtf must be 0):
+ * out[i * OALGPU_MAX_AMBI_CHANNELS + c] <- channel c of sources[i]; the records of channels the format does not have are zeroed,
+ * sources[i].voices is not read.  rot / mix (either may be NULL): count x 25 x 25 floats, row-major, <- the rotation
+ * (DeviceBase::mAmbiRotateMatrix) and the mix matrix (mAmbiRotateMatrix2) of every source; zeroed for a source without
+ * coverage, which builds neither. */
+int oalgpu_ambi_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
+    const oalgpu_slot_environment *slots, const uint8_t *dry_index, const float *dry_scale, const uint8_t *wet_index,
+    const float *wet_scale, const oalgpu_ambi_device *device, uint32_t frequency, const oalgpu_ambi_source *sources,
+    size_t count, oalgpu_voice_params *out, float *rot, float *mix);
+/* Host only.  The tables the stage derives from their definitions: scales[3][25] <- AmbiScale::FromFuMa, FromSN3D, FromN3D
+ * (oalgpu_ambi_scaling's order; FuMa's entries past ACN 15 are 1), index[4][25] <- AmbiIndex::FromFuMa, FromFuMa2D, FromACN,
+ * FromACN2D (entries the table does not have are 0). */
+int oalgpu_ambi_tables_host(float *scales, uint8_t *index);
 
 /* One update: zero the dry/real and wet buses, mix every Playing|Stopping voice
  * (Voice::mix, core/voice.cpp:988-1233), and -- HRTF context, post_process != 0 -- run

@@ -40,6 +40,7 @@
 #include "api_util.hpp"
 #include "kernels.hpp"
 #include "dev_source_nfc.hpp"
+#include "dev_source_ambi.hpp"
 #include "bus_merge.hpp"
 #include "reverb_dev.hpp"
 
@@ -304,6 +305,16 @@ struct oalgpu_context {
     std::vector<uint32_t> srcVoices;        // (the voices of srcHost: a voice named twice keeps its last record)
     DevBuf<ChannelSourceRecord> chanDev;    // channel sources (oalgpu_voice_set_channel_sources): their staging; srcVoices: the
     std::vector<ChannelSourceRecord> chanHost;      // channel voices in the order of their records
+    // ambisonic sources (oalgpu_voice_set_ambi_sources): DeviceBase::mAmbiOrder / m2DMixing (0: not told), the upsamplers the
+    // context was given ([(source order - 1) * 2 + is_2d], kAmbiMatrix floats each, host and device), RotatorCoeffArray on the
+    // device, the records' staging
+    uint32_t ambiOrder{0};
+    bool ambiMix2d{false};
+    bool ambiUpGiven[8]{};
+    std::vector<float> ambiUpHost;
+    DevBuf<float> ambiUpDev, ambiRotDev;
+    DevBuf<AmbiSourceRecord> ambiDev;
+    std::vector<AmbiSourceRecord> ambiHost;
     // callback sources (oalgpu_voice_init_callback): the host's mirror of what Voice::mix keeps for them
     struct CbVoice {
         uint32_t voice{0}; int32_t buffer{-1}; uint32_t frameBytes{4}, capacityFrames{0};

@@ -224,6 +224,81 @@ def channel_source_nfc_host(desc, listener, sources_array, frequency, avg_speake
     return w0, coeffs
 
 
+MAX_AMBI_CHANNELS = MAX_AMBI
+MAX_AMBI_ORDER = 4
+AMBI_LAYOUT_FUMA, AMBI_LAYOUT_ACN = range(2)
+AMBI_SCALING_FUMA, AMBI_SCALING_SN3D, AMBI_SCALING_N3D = range(3)
+
+
+def ambi_source_channels(order, is_2d):
+    """the channel voices of a B-Format source, in the buffer's channel order"""
+    return 2 * order + 1 if is_2d else (order + 1) ** 2
+
+
+class AmbiSource(C.Structure):
+    """oalgpu_ambi_source: a FmtBFormat2D / FmtBFormat3D source of order 1..4, one voice per channel"""
+    _fields_ = [("props", SourceProps), ("spatialize", C.c_int32), ("is_2d", C.c_int32), ("order", C.c_uint32), ("layout", C.c_int32),
+                ("scaling", C.c_int32), ("orient_at", C.c_float * 3), ("orient_up", C.c_float * 3), ("voices", C.c_uint32 * MAX_AMBI_CHANNELS)]
+
+    @classmethod
+    def make(cls, props, order, is_2d=False, spatialize=SPATIALIZE_AUTO, layout=AMBI_LAYOUT_ACN, scaling=AMBI_SCALING_SN3D,
+             orient_at=(0.0, 0.0, -1.0), orient_up=(0.0, 1.0, 0.0), voices=()):
+        s = cls()
+        s.props, s.spatialize, s.is_2d, s.order, s.layout, s.scaling = props, spatialize, int(bool(is_2d)), order, layout, scaling
+        s.orient_at[:] = orient_at
+        s.orient_up[:] = orient_up
+        s.voices[:] = (list(voices) + [NO_VOICE] * MAX_AMBI_CHANNELS)[:MAX_AMBI_CHANNELS]
+        return s
+
+
+class AmbiDevice(C.Structure):
+    """oalgpu_ambi_device: DeviceBase::mAmbiOrder, m2DMixing and the upsamplers [source order - 1][is_2d]"""
+    _fields_ = [("order", C.c_uint32), ("mix_2d", C.c_int32), ("upsampler", (C.c_void_p * 2) * MAX_AMBI_ORDER)]
+
+
+def ambi_source_params_host(desc, listener, sources_array, frequency, order, mix_2d=False, upsamplers=None, slots=None, dry_map=None,
+                            wet_maps=None):
+    """oalgpu_ambi_source_params_host for a ctypes array of AmbiSource on a device of `order`; upsamplers: {(source order, is_2d):
+    rows x 25 float32 array}
+    -> (a ctypes array of VoiceParams, MAX_AMBI_CHANNELS per source; rot[n, 25, 25]; mix[n, 25, 25])"""
+    n = len(sources_array)
+    out = (VoiceParams * (n * MAX_AMBI_CHANNELS))()
+    rot = np.zeros((n, MAX_AMBI_CHANNELS, MAX_AMBI_CHANNELS), np.float32)
+    mix = np.zeros((n, MAX_AMBI_CHANNELS, MAX_AMBI_CHANNELS), np.float32)
+    dev = AmbiDevice()
+    dev.order, dev.mix_2d = order, int(bool(mix_2d))
+    keep = []
+    for (o, is_2d), m in (upsamplers or {}).items():
+        m = np.ascontiguousarray(m, np.float32)
+        assert m.shape == ((o + 1) ** 2, MAX_AMBI_CHANNELS), m.shape
+        keep.append(m)
+        dev.upsampler[o - 1][1 if is_2d else 0] = m.ctypes.data
+    u8p = C.POINTER(C.c_uint8)
+    fn = lib.oalgpu_ambi_source_params_host
+    fn.argtypes = [C.POINTER(ContextDesc), C.POINTER(ListenerParams), C.c_void_p, u8p, f32p, u8p, f32p, C.POINTER(AmbiDevice),
+                   C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, f32p, f32p]
+
+    def maps(m):
+        if m is None:
+            return None, None, None
+        idx = np.ascontiguousarray(m[0], np.uint8); sc = np.ascontiguousarray(m[1], np.float32)
+        return idx.ctypes.data_as(u8p), _fp(sc), (idx, sc)
+    di, ds, keep_d = maps(dry_map)
+    wi, ws, keep_w = maps(wet_maps)
+    check(fn(C.byref(desc), C.byref(listener), C.cast(slots, C.c_void_p) if slots is not None else None, di, ds, wi, ws, C.byref(dev),
+             frequency, C.cast(sources_array, C.c_void_p), n, C.cast(out, C.c_void_p), _fp(rot), _fp(mix)), "oalgpu_ambi_source_params_host")
+    return out, rot, mix
+
+
+def ambi_tables_host():
+    """oalgpu_ambi_tables_host -> (scales[3, 25]: FromFuMa, FromSN3D, FromN3D; index[4, 25]: FromFuMa, FromFuMa2D, FromACN, FromACN2D)"""
+    scales = np.zeros((3, MAX_AMBI_CHANNELS), np.float32)
+    index = np.zeros((4, MAX_AMBI_CHANNELS), np.uint8)
+    lib.oalgpu_ambi_tables_host.argtypes = [f32p, C.POINTER(C.c_uint8)]
+    check(lib.oalgpu_ambi_tables_host(_fp(scales), index.ctypes.data_as(C.POINTER(C.c_uint8))), "oalgpu_ambi_tables_host")
+    return scales, index
+
+
 def nfc_adjust_host(w1, w0):
     """oalgpu_nfc_adjust_host: what oalgpu_voice_set_nfc(voice, w0) designs on a context of oalgpu_context_set_nfc(w1) -> coeffs[14]"""
     coeffs = np.zeros(14, np.float32)
@@ -747,6 +822,31 @@ class Scene:
         lib.oalgpu_param_block_create_from_channel_sources.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         check(lib.oalgpu_param_block_create_from_channel_sources(self.h, C.cast(sources_array, C.c_void_p), len(sources_array),
                                                                  C.byref(h)), "oalgpu_param_block_create_from_channel_sources")
+        return h
+
+    # the same for B-Format sources: the device's order, the upsamplers it needs, one voice per channel
+    def set_ambi_order(self, order, mix_2d=False):
+        lib.oalgpu_context_set_ambi_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
+        check(lib.oalgpu_context_set_ambi_order(self.h, order, int(bool(mix_2d))), "oalgpu_context_set_ambi_order")
+
+    def set_ambi_upsampler(self, source_order, is_2d, matrix):
+        """matrix: rows x 25 (one of AmbiScale::FirstOrderUp .. FourthOrder2DUp)"""
+        m = np.ascontiguousarray(matrix, np.float32)
+        lib.oalgpu_context_set_ambi_upsampler.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, f32p, C.c_uint32]
+        check(lib.oalgpu_context_set_ambi_upsampler(self.h, source_order, int(bool(is_2d)), _fp(m), m.shape[0]),
+              "oalgpu_context_set_ambi_upsampler")
+
+    def set_ambi_sources(self, sources_array):
+        """sources_array: ctypes array of AmbiSource"""
+        lib.oalgpu_voice_set_ambi_sources.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        check(lib.oalgpu_voice_set_ambi_sources(self.h, C.cast(sources_array, C.c_void_p), len(sources_array)),
+              "oalgpu_voice_set_ambi_sources")
+
+    def param_block_from_ambi_sources(self, sources_array):
+        h = C.c_void_p()
+        lib.oalgpu_param_block_create_from_ambi_sources.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        check(lib.oalgpu_param_block_create_from_ambi_sources(self.h, C.cast(sources_array, C.c_void_p), len(sources_array),
+                                                              C.byref(h)), "oalgpu_param_block_create_from_ambi_sources")
         return h
 
     # near-field control (same interface as tests/oracle_lib.Scene)
