@@ -1,9 +1,13 @@
-// 3D source parameters computed on the GPU: the listener, the slots' send environments, and the entry points that turn source
-// properties into parameter records with SourceParamsKernel (source_kernels.hip) -- and the same arithmetic (dev_source.hpp)
-// compiled for the host, oalgpu_source_params_host.  The same for multi-channel and non-spatialized sources: channel sources,
-// ChannelParamsKernel (source_channel_kernels.hip), dev_source_channels.hpp, oalgpu_channel_source_params_host.  On a context with
-// near-field control that knows its speaker distance the same entry points also run the near-field side: SourceNfcKernel and
-// ApplyNfcKernel (source_nfc_kernels.hip), dev_source_nfc.hpp, oalgpu_channel_source_nfc_host.
+// Source parameters computed on the GPU: the listener, the slots' send environments, and the entry points that turn source
+// properties into parameter records.  Three kinds of source, each with a collector (what the call refuses; the kind's records
+// and the voices in output order), a params kernel and the same arithmetic compiled for the host:
+//   mono 3D sources      CollectSources          SourceParamsKernel (source_kernels.hip)           dev_source.hpp           oalgpu_source_params_host
+//   channel sources      CollectChannelSources   ChannelParamsKernel (source_channel_kernels.hip)  dev_source_channels.hpp  oalgpu_channel_source_params_host
+//   ambisonic sources    CollectAmbiSources      AmbiParamsKernel (source_ambi_kernels.hip)        dev_source_ambi.hpp      oalgpu_ambi_source_params_host
+// Behind the collector every entry point is one of two paths over the kind's launch: ApplyCollected (the synchronous call) or
+// BlockFromCollected (a parameter block).  On a context with near-field control that knows its speaker distance the first two
+// kinds' launches also run the near-field side: SourceNfcKernel and ApplyNfcKernel (source_nfc_kernels.hip), dev_source_nfc.hpp,
+// oalgpu_channel_source_nfc_host.
 #include "api_context.hpp"
 
 namespace {
@@ -61,22 +65,46 @@ SourceSetup SetupOf(const oalgpu_context *c)
         c->slotEnv.p, c->rsConsts.p, c->dryMap.p, c->wetMaps.p};
 }
 
-// the near-field side of a call (contexts with near-field control): SourceNfcKernel over the staged records the params kernel
-// of the same call reads -- `mono` or `chan`, the other null -- into `out`, on the context's stream beside it
-int RunNfcStage(oalgpu_context *c, const SourceRecord *mono, const ChannelSourceRecord *chan, size_t sources, NfcRecord *out)
-{
-    LaunchSourceNfc(c->stream, SetupOf(c), c->listener, NfcSetupOf(c), mono, chan, uint32_t(sources), out);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
+// ---- the collectors: what a call refuses, and of what it accepts the kind's source records (c->srcHost, c->chanHost or
+// c->ambiHost, with their places in the output) and the voices in output order (c->srcVoices) ----
 
-// what both entry points refuse, and the source records of what they accept (c->srcHost)
-int CollectSources(oalgpu_context *c, const char *who, const uint32_t *voices, const oalgpu_source_props *props, size_t count)
+// the contexts the pan-gain kinds refuse
+int StageContextOk(const oalgpu_context *c, const std::string &name)
 {
-    const std::string name(who);
     if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, name + ": HRTF context without a data set");
     if(c->L.nfc && !(c->nfcAvgDist > 0.0f))
         return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control whose speaker distance is not set (oalgpu_context_set_nfc_distance; without it the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
+    return OALGPU_OK;
+}
+
+bool ChannelSourceOk(const oalgpu_channel_source &src)
+{
+    return src.channels >= OALGPU_CHANNELS_MONO && src.channels <= OALGPU_CHANNELS_X71 && src.spatialize >= OALGPU_SPATIALIZE_OFF
+        && src.spatialize <= OALGPU_SPATIALIZE_AUTO;
+}
+
+// one channel voice of a multi-channel source: what is refused of it; otherwise it is named, `frequency` (0: the source's
+// first voice) is the source's, and the voice is next in the output
+int ClaimChannelVoice(oalgpu_context *c, const std::string &name, uint32_t v, std::vector<uint8_t> &named, uint32_t &frequency)
+{
+    if(v >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, name + ": bad voice index");
+    if(c->cbOfVoice[v] >= 0)
+        return Fail(OALGPU_ERR_INVALID, name + ": not for callback voices (their step is mirrored on the host: oalgpu_voice_set_params)");
+    if(named[v]) return Fail(OALGPU_ERR_INVALID, name + ": a voice named twice");
+    named[v] = 1;
+    const uint32_t freq = v < c->voiceFreq.size() ? c->voiceFreq[v] : 0u;
+    if(freq == 0u) return Fail(OALGPU_ERR_INVALID, name + ": the voice has no frequency (start it with oalgpu_voice_init)");
+    if(frequency && frequency != freq)
+        return Fail(OALGPU_ERR_INVALID, name + ": the channel voices of a source have different frequencies");
+    frequency = freq;
+    c->srcVoices.push_back(v);
+    return OALGPU_OK;
+}
+
+int CollectSources(oalgpu_context *c, const char *who, const uint32_t *voices, const oalgpu_source_props *props, size_t count)
+{
+    const std::string name(who);
+    if(int rc = StageContextOk(c, name)) return rc;
     for(size_t i = 0; i < count; ++i)
     {
         if(voices[i] >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, name + ": bad voice index");
@@ -100,22 +128,16 @@ int CollectSources(oalgpu_context *c, const char *who, const uint32_t *voices, c
     return OALGPU_OK;
 }
 
-// the same for channel sources: the records (c->chanHost, with their places in the output) and the voices in output order
-// (c->srcVoices)
 int CollectChannelSources(oalgpu_context *c, const char *who, const oalgpu_channel_source *sources, size_t count)
 {
     const std::string name(who);
-    if(c->L.hrtf && !c->hrtfLoaded) return Fail(OALGPU_ERR_NO_HRTF, name + ": HRTF context without a data set");
-    if(c->L.nfc && !(c->nfcAvgDist > 0.0f))
-        return Fail(OALGPU_ERR_INVALID, name + ": not for contexts with near-field control whose speaker distance is not set (oalgpu_context_set_nfc_distance; without it the per-voice w0 adjust stays with the host: oalgpu_voice_set_nfc)");
+    if(int rc = StageContextOk(c, name)) return rc;
     std::vector<uint8_t> named(c->L.numVoices, 0);
     c->chanHost.clear(); c->srcVoices.clear();
     for(size_t i = 0; i < count; ++i)
     {
         const oalgpu_channel_source &src = sources[i];
-        if(src.channels < OALGPU_CHANNELS_MONO || src.channels > OALGPU_CHANNELS_X71 || src.spatialize < OALGPU_SPATIALIZE_OFF
-            || src.spatialize > OALGPU_SPATIALIZE_AUTO)
-            return Fail(OALGPU_ERR_INVALID, name + ": channels or spatialize out of range");
+        if(!ChannelSourceOk(src)) return Fail(OALGPU_ERR_INVALID, name + ": channels or spatialize out of range");
         if(!PropsOk(src.props, c->L.numSends, c->L.numSlots))
             return Fail(OALGPU_ERR_INVALID, name + ": resampler, distance model or send slot out of range");
         ChannelSourceRecord rec{};
@@ -128,19 +150,9 @@ int CollectChannelSources(oalgpu_context *c, const char *who, const oalgpu_chann
         {
             const uint32_t v = src.voices[ch];
             if(v == OALGPU_NO_VOICE) continue;
-            if(v >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, name + ": bad voice index");
-            if(c->cbOfVoice[v] >= 0)
-                return Fail(OALGPU_ERR_INVALID, name + ": not for callback voices (their step is mirrored on the host: oalgpu_voice_set_params)");
-            if(named[v]) return Fail(OALGPU_ERR_INVALID, name + ": a voice named twice");
-            named[v] = 1;
-            const uint32_t freq = v < c->voiceFreq.size() ? c->voiceFreq[v] : 0u;
-            if(freq == 0u) return Fail(OALGPU_ERR_INVALID, name + ": the voice has no frequency (start it with oalgpu_voice_init)");
-            if(rec.frequency && rec.frequency != freq)
-                return Fail(OALGPU_ERR_INVALID, name + ": the channel voices of a source have different frequencies");
-            rec.frequency = freq;
+            if(int rc = ClaimChannelVoice(c, name, v, named, rec.frequency)) return rc;
             rec.voices[ch] = v;
             rec.present |= 1u << ch;
-            c->srcVoices.push_back(v);
         }
         if(!rec.frequency) return Fail(OALGPU_ERR_INVALID, name + ": a source without a channel voice");
         c->chanHost.push_back(rec);
@@ -189,11 +201,10 @@ struct HostStage {
     }
 };
 
-// what the stage leaves for one channel voice, as an oalgpu_voice_params: the filters' parameters in place of the designs,
-// the resolved line gains
-void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const SourceGains &g, const ChannelPan &pan, const HostStage &h)
+// what the stage leaves for one voice whatever pans it, as an oalgpu_voice_params cleared otherwise: the step, the resampler,
+// the filters' parameters in place of the designs, the send slots
+void FillVoiceCommon(oalgpu_voice_params &o, const oalgpu_source_props &p, const SourceGains &g, const SourceSetup &cx)
 {
-    const SourceSetup &cx = h.cx;
     std::memset(&o, 0, sizeof(o));
     const uint32_t flags = SourceFilterFlags(g, cx.numSends);
     o.step = g.step;
@@ -201,6 +212,20 @@ void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const
     const float invSampleRate = 1.0f / float(cx.sampleRate);
     o.direct_filter = oalgpu_filter_params{(flags & kFlagDirectFilter) ? 1 : 0, g.dryHF, p.direct_hf_reference * invSampleRate,
         g.dryLF, p.direct_lf_reference * invSampleRate};
+    for(uint32_t s = 0; s < OALGPU_MAX_SENDS; ++s)
+    {
+        o.send_slot[s] = g.sendSlot[s];
+        if(s < cx.numSends)
+            o.send_filter[s] = oalgpu_filter_params{(flags >> (kFlagSendFilterShift + s)) & 1u ? 1 : 0, g.wetHF[s],
+                p.send[s].hf_reference * invSampleRate, g.wetLF[s], p.send[s].lf_reference * invSampleRate};
+    }
+}
+
+// the same with the resolved line gains of a voice panned by a direction
+void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const SourceGains &g, const ChannelPan &pan, const HostStage &h)
+{
+    const SourceSetup &cx = h.cx;
+    FillVoiceCommon(o, p, g, cx);
     o.hrtf_ev = pan.hrtfEv; o.hrtf_az = pan.hrtfAz; o.hrtf_dist = pan.hrtfDist; o.hrtf_spread = pan.hrtfSpread;
     const float dryGain = g.dryBase * pan.pangain;
     o.hrtf_gain = dryGain;
@@ -208,12 +233,8 @@ void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const
     if(!cx.hrtf && !pan.silent)
         for(uint32_t t = 0; t < cx.numDry; ++t)
             o.dry_gains[t] = PanLineGain(h.dryMap[t].index, h.dryMap[t].scale, ay, az, ax, pan.drySpread, dryGain);
-    for(uint32_t s = 0; s < OALGPU_MAX_SENDS; ++s)
+    for(uint32_t s = 0; s < cx.numSends; ++s)
     {
-        o.send_slot[s] = g.sendSlot[s];
-        if(s >= cx.numSends) continue;
-        o.send_filter[s] = oalgpu_filter_params{(flags >> (kFlagSendFilterShift + s)) & 1u ? 1 : 0, g.wetHF[s],
-            p.send[s].hf_reference * invSampleRate, g.wetLF[s], p.send[s].lf_reference * invSampleRate};
         if(g.sendSlot[s] < 0 || pan.silent) continue;
         for(uint32_t ch = 0; ch < cx.wetChannels; ++ch)
         {
@@ -221,6 +242,74 @@ void FillVoiceParams(oalgpu_voice_params &o, const oalgpu_source_props &p, const
             o.send_gains[s][ch] = PanLineGain(m.index, m.scale, ay, az, ax, pan.sendSpread, g.wetBase[s] * pan.pangain);
         }
     }
+}
+
+// ---- a collected call on the device.  The collector has left the kind's records and c->srcVoices; the kind's launch -- a
+// StageLaunch -- stages the records and launches its params kernel into `out` and, on near-field contexts, SourceNfcKernel over
+// the same staged records into `nfcOut`, on the context's stream.  Two consumers: the synchronous call and the block. ----
+using StageLaunch = int (*)(oalgpu_context *c, ParamRecord *out, NfcRecord *nfcOut);
+
+int RunNfcStage(oalgpu_context *c, const SourceRecord *mono, const ChannelSourceRecord *chan, size_t sources, NfcRecord *out)
+{
+    if(!c->L.nfc) return OALGPU_OK;
+    LaunchSourceNfc(c->stream, SetupOf(c), c->listener, NfcSetupOf(c), mono, chan, uint32_t(sources), out);
+    HIP_TRY(hipGetLastError());
+    return OALGPU_OK;
+}
+
+int LaunchMonoStage(oalgpu_context *c, ParamRecord *out, NfcRecord *nfcOut)
+{
+    const size_t count = c->srcHost.size();
+    if(int rc = StageRecords(c->stream, c->srcDev, c->srcHost.data(), count)) return rc;
+    LaunchSourceParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->srcDev.p, uint32_t(count), out);
+    HIP_TRY(hipGetLastError());
+    return RunNfcStage(c, c->srcDev.p, nullptr, count, nfcOut);
+}
+
+int LaunchChannelStage(oalgpu_context *c, ParamRecord *out, NfcRecord *nfcOut)
+{
+    const size_t count = c->chanHost.size();
+    if(int rc = StageRecords(c->stream, c->chanDev, c->chanHost.data(), count)) return rc;
+    uint32_t maxChannels = 1;
+    for(const ChannelSourceRecord &r : c->chanHost) maxChannels = std::max(maxChannels, SourceChannelCount(r.channels));
+    LaunchChannelParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->chanDev.p, uint32_t(count), maxChannels, out);
+    HIP_TRY(hipGetLastError());
+    return RunNfcStage(c, nullptr, c->chanDev.p, count, nfcOut);
+}
+
+// the records into c->paramDev / c->nfcRecDev, installed in the voices: params, NFC, apply params, apply NFC, synchronize
+int ApplyCollected(oalgpu_context *c, StageLaunch launch)
+{
+    if(int rc = BeginVoiceCall(c)) return rc;
+    if(int rc = EnsureSourceStage(c)) return rc;
+    const size_t records = c->srcVoices.size();
+    if(c->paramDev.n < records) HIP_TRY(c->paramDev.alloc(records));
+    if(c->L.nfc && c->nfcRecDev.n < records) HIP_TRY(c->nfcRecDev.alloc(records));
+    if(int rc = launch(c, c->paramDev.p, c->nfcRecDev.p)) return rc;
+    LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(records));
+    HIP_TRY(hipGetLastError());
+    if(c->L.nfc) { ApplyNfcRecords(c, c->nfcRecDev.p, uint32_t(records)); HIP_TRY(hipGetLastError()); }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OALGPU_OK;
+}
+
+// the records into a new block
+int BlockFromCollected(oalgpu_context *c, StageLaunch launch, oalgpu_param_block **out)
+{
+    if(int rc = UseCtx(c)) return rc;
+    if(int rc = EnsureSourceStage(c)) return rc;
+    const size_t records = c->srcVoices.size();
+    auto b = std::make_unique<oalgpu_param_block>();
+    b->count = uint32_t(records);
+    b->device = c->desc.device;
+    b->hrtfGeneration = c->hrtfGeneration;
+    HIP_TRY(b->recs.alloc(records));
+    if(c->L.nfc) HIP_TRY(b->nfc.alloc(records));
+    if(int rc = launch(c, b->recs.p, b->nfc.p)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
+    if(int rc = FinishParamBlock(c, b.get(), c->srcVoices.data(), records)) return rc;
+    *out = b.release();
+    return OALGPU_OK;
 }
 
 } // namespace
@@ -264,20 +353,7 @@ int oalgpu_voice_set_source_props(oalgpu_context *c, const uint32_t *voices, con
     if(!c || !voices || !props) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_source_props: null argument");
     if(count == 0) return OALGPU_OK;
     if(int rc = CollectSources(c, "oalgpu_voice_set_source_props", voices, props, count)) return rc;
-    if(int rc = BeginVoiceCall(c)) return rc;
-    if(int rc = EnsureSourceStage(c)) return rc;
-    count = c->srcHost.size();
-    if(int rc = StageRecords(c->stream, c->srcDev, c->srcHost.data(), count)) return rc;
-    if(c->paramDev.n < count) HIP_TRY(c->paramDev.alloc(count));
-    if(c->L.nfc && c->nfcRecDev.n < count) HIP_TRY(c->nfcRecDev.alloc(count));
-    LaunchSourceParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->srcDev.p, uint32_t(count), c->paramDev.p);
-    HIP_TRY(hipGetLastError());
-    if(c->L.nfc) { if(int rc = RunNfcStage(c, c->srcDev.p, nullptr, count, c->nfcRecDev.p)) return rc; }
-    LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(count));
-    HIP_TRY(hipGetLastError());
-    if(c->L.nfc) { ApplyNfcRecords(c, c->nfcRecDev.p, uint32_t(count)); HIP_TRY(hipGetLastError()); }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return OALGPU_OK;
+    return ApplyCollected(c, LaunchMonoStage);
 }
 
 int oalgpu_param_block_create_from_sources(oalgpu_context *c, const uint32_t *voices, const oalgpu_source_props *props, size_t count,
@@ -287,24 +363,7 @@ int oalgpu_param_block_create_from_sources(oalgpu_context *c, const uint32_t *vo
         return Fail(OALGPU_ERR_INVALID, "oalgpu_param_block_create_from_sources: bad arguments");
     *out = nullptr;
     if(int rc = CollectSources(c, "oalgpu_param_block_create_from_sources", voices, props, count)) return rc;
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = EnsureSourceStage(c)) return rc;
-    count = c->srcHost.size();
-    voices = c->srcVoices.data();
-    auto b = std::make_unique<oalgpu_param_block>();
-    b->count = uint32_t(count);
-    b->device = c->desc.device;
-    b->hrtfGeneration = c->hrtfGeneration;
-    HIP_TRY(b->recs.alloc(count));
-    if(int rc = StageRecords(c->stream, c->srcDev, c->srcHost.data(), count)) return rc;
-    if(c->L.nfc) HIP_TRY(b->nfc.alloc(count));
-    LaunchSourceParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->srcDev.p, uint32_t(count), b->recs.p);
-    HIP_TRY(hipGetLastError());
-    if(c->L.nfc) { if(int rc = RunNfcStage(c, c->srcDev.p, nullptr, count, b->nfc.p)) return rc; }
-    HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
-    if(int rc = FinishParamBlock(c, b.get(), voices, count)) return rc;
-    *out = b.release();
-    return OALGPU_OK;
+    return BlockFromCollected(c, LaunchMonoStage, out);
 }
 
 int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
@@ -327,34 +386,12 @@ int oalgpu_source_params_host(const oalgpu_context_desc *desc, const oalgpu_list
     return OALGPU_OK;
 }
 
-// the channel sources of c->chanHost -> their records at `out`
-static int RunChannelStage(oalgpu_context *c, ParamRecord *out)
-{
-    if(int rc = StageRecords(c->stream, c->chanDev, c->chanHost.data(), c->chanHost.size())) return rc;
-    uint32_t maxChannels = 1;
-    for(const ChannelSourceRecord &r : c->chanHost) maxChannels = std::max(maxChannels, SourceChannelCount(r.channels));
-    LaunchChannelParams(c->stream, SetupOf(c), c->hrtfDev, c->listener, c->chanDev.p, uint32_t(c->chanHost.size()), maxChannels, out);
-    HIP_TRY(hipGetLastError());
-    return OALGPU_OK;
-}
-
 int oalgpu_voice_set_channel_sources(oalgpu_context *c, const oalgpu_channel_source *sources, size_t count)
 {
     if(!c || !sources) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_channel_sources: null argument");
     if(count == 0) return OALGPU_OK;
     if(int rc = CollectChannelSources(c, "oalgpu_voice_set_channel_sources", sources, count)) return rc;
-    if(int rc = BeginVoiceCall(c)) return rc;
-    if(int rc = EnsureSourceStage(c)) return rc;
-    const size_t records = c->srcVoices.size();
-    if(c->paramDev.n < records) HIP_TRY(c->paramDev.alloc(records));
-    if(c->L.nfc && c->nfcRecDev.n < records) HIP_TRY(c->nfcRecDev.alloc(records));
-    if(int rc = RunChannelStage(c, c->paramDev.p)) return rc;
-    if(c->L.nfc) { if(int rc = RunNfcStage(c, nullptr, c->chanDev.p, c->chanHost.size(), c->nfcRecDev.p)) return rc; }
-    LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(records));
-    HIP_TRY(hipGetLastError());
-    if(c->L.nfc) { ApplyNfcRecords(c, c->nfcRecDev.p, uint32_t(records)); HIP_TRY(hipGetLastError()); }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return OALGPU_OK;
+    return ApplyCollected(c, LaunchChannelStage);
 }
 
 int oalgpu_param_block_create_from_channel_sources(oalgpu_context *c, const oalgpu_channel_source *sources, size_t count,
@@ -364,21 +401,7 @@ int oalgpu_param_block_create_from_channel_sources(oalgpu_context *c, const oalg
         return Fail(OALGPU_ERR_INVALID, "oalgpu_param_block_create_from_channel_sources: bad arguments");
     *out = nullptr;
     if(int rc = CollectChannelSources(c, "oalgpu_param_block_create_from_channel_sources", sources, count)) return rc;
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = EnsureSourceStage(c)) return rc;
-    const size_t records = c->srcVoices.size();
-    auto b = std::make_unique<oalgpu_param_block>();
-    b->count = uint32_t(records);
-    b->device = c->desc.device;
-    b->hrtfGeneration = c->hrtfGeneration;
-    HIP_TRY(b->recs.alloc(records));
-    if(c->L.nfc) HIP_TRY(b->nfc.alloc(records));
-    if(int rc = RunChannelStage(c, b->recs.p)) return rc;
-    if(c->L.nfc) { if(int rc = RunNfcStage(c, nullptr, c->chanDev.p, c->chanHost.size(), b->nfc.p)) return rc; }
-    HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
-    if(int rc = FinishParamBlock(c, b.get(), c->srcVoices.data(), records)) return rc;
-    *out = b.release();
-    return OALGPU_OK;
+    return BlockFromCollected(c, LaunchChannelStage, out);
 }
 
 int oalgpu_channel_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
@@ -393,9 +416,7 @@ int oalgpu_channel_source_params_host(const oalgpu_context_desc *desc, const oal
     for(size_t i = 0; i < count; ++i)
     {
         const oalgpu_channel_source &src = sources[i];
-        if(src.channels < OALGPU_CHANNELS_MONO || src.channels > OALGPU_CHANNELS_X71 || src.spatialize < OALGPU_SPATIALIZE_OFF
-            || src.spatialize > OALGPU_SPATIALIZE_AUTO)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_params_host: channels or spatialize out of range");
+        if(!ChannelSourceOk(src)) return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_params_host: channels or spatialize out of range");
         if(!PropsOk(src.props, h.cx.numSends, h.cx.numSlots))
             return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_params_host: resampler, distance model or send slot out of range");
     }
@@ -426,9 +447,7 @@ int oalgpu_channel_source_nfc_host(const oalgpu_context_desc *desc, const oalgpu
     for(size_t i = 0; i < count; ++i)
     {
         const oalgpu_channel_source &src = sources[i];
-        if(src.channels < OALGPU_CHANNELS_MONO || src.channels > OALGPU_CHANNELS_X71 || src.spatialize < OALGPU_SPATIALIZE_OFF
-            || src.spatialize > OALGPU_SPATIALIZE_AUTO)
-            return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_nfc_host: channels or spatialize out of range");
+        if(!ChannelSourceOk(src)) return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_nfc_host: channels or spatialize out of range");
         if(!PropsOk(src.props, h.cx.numSends, h.cx.numSlots))
             return Fail(OALGPU_ERR_INVALID, "oalgpu_channel_source_nfc_host: resampler, distance model or send slot out of range");
     }
@@ -560,19 +579,9 @@ int CollectAmbiSources(oalgpu_context *c, const char *who, const oalgpu_ambi_sou
         {
             const uint32_t v = src.voices[ch];
             if(v == OALGPU_NO_VOICE) continue;
-            if(v >= c->L.numVoices) return Fail(OALGPU_ERR_INVALID, name + ": bad voice index");
-            if(c->cbOfVoice[v] >= 0)
-                return Fail(OALGPU_ERR_INVALID, name + ": not for callback voices (their step is mirrored on the host: oalgpu_voice_set_params)");
-            if(named[v]) return Fail(OALGPU_ERR_INVALID, name + ": a voice named twice");
-            named[v] = 1;
-            const uint32_t freq = v < c->voiceFreq.size() ? c->voiceFreq[v] : 0u;
-            if(freq == 0u) return Fail(OALGPU_ERR_INVALID, name + ": the voice has no frequency (start it with oalgpu_voice_init)");
-            if(rec.frequency && rec.frequency != freq)
-                return Fail(OALGPU_ERR_INVALID, name + ": the channel voices of a source have different frequencies");
-            rec.frequency = freq;
+            if(int rc = ClaimChannelVoice(c, name, v, named, rec.frequency)) return rc;
             rec.voices[ch] = v;
             rec.present |= 1u << ch;
-            c->srcVoices.push_back(v);
         }
         if(!rec.frequency) return Fail(OALGPU_ERR_INVALID, name + ": a source without a channel voice");
         c->ambiHost.push_back(rec);
@@ -597,9 +606,10 @@ int EnsureAmbiStage(oalgpu_context *c)
     return OALGPU_OK;
 }
 
-// the ambisonic sources of c->ambiHost -> their records at `out`
-int RunAmbiStage(oalgpu_context *c, ParamRecord *out)
+// the ambisonic kind's StageLaunch (no near-field side: the collector refuses those contexts)
+int LaunchAmbiStage(oalgpu_context *c, ParamRecord *out, NfcRecord *)
 {
+    if(int rc = EnsureAmbiStage(c)) return rc;
     if(int rc = StageRecords(c->stream, c->ambiDev, c->ambiHost.data(), c->ambiHost.size())) return rc;
     LaunchAmbiParams(c->stream, SetupOf(c), AmbiSetup{c->ambiOrder, c->ambiRotDev.p, c->ambiUpDev.p}, c->listener, c->ambiDev.p,
         uint32_t(c->ambiHost.size()), out);
@@ -637,16 +647,7 @@ int oalgpu_voice_set_ambi_sources(oalgpu_context *c, const oalgpu_ambi_source *s
     if(!c || !sources) return Fail(OALGPU_ERR_INVALID, "oalgpu_voice_set_ambi_sources: null argument");
     if(count == 0) return OALGPU_OK;
     if(int rc = CollectAmbiSources(c, "oalgpu_voice_set_ambi_sources", sources, count)) return rc;
-    if(int rc = BeginVoiceCall(c)) return rc;
-    if(int rc = EnsureSourceStage(c)) return rc;
-    if(int rc = EnsureAmbiStage(c)) return rc;
-    const size_t records = c->srcVoices.size();
-    if(c->paramDev.n < records) HIP_TRY(c->paramDev.alloc(records));
-    if(int rc = RunAmbiStage(c, c->paramDev.p)) return rc;
-    LaunchApplyParams(c->stream, c->L, c->paramDev.p, uint32_t(records));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return OALGPU_OK;
+    return ApplyCollected(c, LaunchAmbiStage);
 }
 
 int oalgpu_param_block_create_from_ambi_sources(oalgpu_context *c, const oalgpu_ambi_source *sources, size_t count,
@@ -656,20 +657,7 @@ int oalgpu_param_block_create_from_ambi_sources(oalgpu_context *c, const oalgpu_
         return Fail(OALGPU_ERR_INVALID, "oalgpu_param_block_create_from_ambi_sources: bad arguments");
     *out = nullptr;
     if(int rc = CollectAmbiSources(c, "oalgpu_param_block_create_from_ambi_sources", sources, count)) return rc;
-    if(int rc = UseCtx(c)) return rc;
-    if(int rc = EnsureSourceStage(c)) return rc;
-    if(int rc = EnsureAmbiStage(c)) return rc;
-    const size_t records = c->srcVoices.size();
-    auto b = std::make_unique<oalgpu_param_block>();
-    b->count = uint32_t(records);
-    b->device = c->desc.device;
-    b->hrtfGeneration = c->hrtfGeneration;
-    HIP_TRY(b->recs.alloc(records));
-    if(int rc = RunAmbiStage(c, b->recs.p)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));       // (the staging is free again; the rows below read finished records)
-    if(int rc = FinishParamBlock(c, b.get(), c->srcVoices.data(), records)) return rc;
-    *out = b.release();
-    return OALGPU_OK;
+    return BlockFromCollected(c, LaunchAmbiStage, out);
 }
 
 int oalgpu_ambi_source_params_host(const oalgpu_context_desc *desc, const oalgpu_listener_params *listener,
@@ -733,18 +721,12 @@ int oalgpu_ambi_source_params_host(const oalgpu_context_desc *desc, const oalgpu
         if(rot_out) std::copy(rot.begin(), rot.end(), rot_out + i * kAmbiMatrix);
         if(mix_out) std::copy(mix.begin(), mix.end(), mix_out + i * kAmbiMatrix);
 
-        const uint32_t flags = SourceFilterFlags(g, cx.numSends);
-        const float invSampleRate = 1.0f / float(cx.sampleRate);
         const float pannedScale = (1.0f - coverage) * rec.scale0;
         for(uint32_t ch = 0; ch < kAmbiMax; ++ch)
         {
             oalgpu_voice_params &o = out[i * kAmbiMax + ch];
-            std::memset(&o, 0, sizeof(o));
-            if(ch >= rec.channels) continue;
-            o.step = g.step;
-            o.resampler = p.resampler;
-            o.direct_filter = oalgpu_filter_params{(flags & kFlagDirectFilter) ? 1 : 0, g.dryHF, p.direct_hf_reference * invSampleRate,
-                g.dryLF, p.direct_lf_reference * invSampleRate};
+            if(ch >= rec.channels) { std::memset(&o, 0, sizeof(o)); continue; }
+            FillVoiceCommon(o, p, g, cx);
             const uint32_t row = uint32_t(rec.acn[ch]) * kAmbiMax;
             const float scale = rec.scale[ch] * coverage;
             auto line = [&](const AmbiMapEntry &m, float base) {
@@ -752,12 +734,8 @@ int oalgpu_ambi_source_params_host(const oalgpu_context_desc *desc, const oalgpu
                 return ch == 0u ? AmbiLineGain(m.scale, panned[m.index], base * rec.scale0) : 0.0f;
             };
             for(uint32_t t = 0; t < cx.numDry; ++t) o.dry_gains[t] = line(h.dryMap[t], g.dryBase);
-            for(uint32_t s = 0; s < OALGPU_MAX_SENDS; ++s)
+            for(uint32_t s = 0; s < cx.numSends; ++s)
             {
-                o.send_slot[s] = g.sendSlot[s];
-                if(s >= cx.numSends) continue;
-                o.send_filter[s] = oalgpu_filter_params{(flags >> (kFlagSendFilterShift + s)) & 1u ? 1 : 0, g.wetHF[s],
-                    p.send[s].hf_reference * invSampleRate, g.wetLF[s], p.send[s].lf_reference * invSampleRate};
                 if(g.sendSlot[s] < 0) continue;
                 for(uint32_t wc = 0; wc < cx.wetChannels; ++wc)
                     o.send_gains[s][wc] = line(h.wetMaps[size_t(g.sendSlot[s]) * cx.wetChannels + wc], g.wetBase[s]);

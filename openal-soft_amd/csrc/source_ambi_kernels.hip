@@ -10,32 +10,19 @@
 // order, a band's (2l + 1)^2 elements spread over the lanes (band 4 has 81: two rounds), a barrier between the bands since
 // band l reads band l - 1.  The upsample is one output column per lane (lanes < 25), rows and k in the reference's order; without an
 // upsampler the mix matrix is the rotation, copied.  Then, for each channel that has a voice, in channel order: the lanes that hold a dry
-// line's or a send line's dword of the record form that gain from the channel's row of the mix matrix, and the record's 283
-// dwords leave in five coalesced passes (SourceParamsKernel's shape); everything but the voice and the gains is formed once,
-// before the channels.  Output is dense: record outBase + (the channels before this one that have a voice).
+// line's or a send line's dword of the record form that gain from the channel's row of the mix matrix, and the record leaves in
+// dev_source_store.hpp's passes, its head and filter dwords by that header's pieces; everything but the voice and the gains is
+// formed once, before the channels.  Output is dense: record outBase + (the channels before this one that have a voice).
 // A source without coverage skips the matrices.  No scratch, no spill (tests/test_ambi_kernel_resources.py).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <stddef.h>
 #include "dev_source_ambi.hpp"
+#include "dev_source_store.hpp"
 
 #pragma clang fp contract(off)
 
 namespace oalgpu {
 namespace {
-
-constexpr uint32_t kRecordDwords = sizeof(ParamRecord) / 4u;
-constexpr uint32_t kOffFilters = offsetof(ParamRecord, dirLp) / 4u;         // dirLp | dirHp | sendLp[6] | sendHp[6]: 14 x 5
-constexpr uint32_t kOffHrtfDir = offsetof(ParamRecord, hrtfDir) / 4u;
-constexpr uint32_t kOffDryGains = offsetof(ParamRecord, dryGains) / 4u;
-constexpr uint32_t kOffSendGains = offsetof(ParamRecord, sendGains) / 4u;
-constexpr uint32_t kOffHrtfIdx = offsetof(ParamRecord, hrtfIdx) / 4u;
-constexpr uint32_t kPasses = (kRecordDwords + 63u) / 64u;
-static_assert(kRecordDwords == 283 && kOffFilters == 14 && kOffHrtfDir == kOffFilters + 70 && kOffDryGains == kOffHrtfDir + 5
-    && kOffSendGains == kOffDryGains + 32 && kOffHrtfIdx == kOffSendGains + 150 && kOffHrtfIdx + 12 == kRecordDwords,
-    "AmbiParamsKernel stores ParamRecord dword by dword");
-
-__device__ __forceinline__ uint32_t Bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 
 // a[k] for a run-time k without indexing the array
 __device__ __forceinline__ float Pick9(const float (&a)[9], uint32_t k)
@@ -69,37 +56,17 @@ __global__ void __launch_bounds__(64) AmbiParamsKernel(SourceSetup cx, AmbiSetup
 
     // what every channel voice's record shares: all dwords but the voice and the line gains; and of the lanes that hold a line
     // gain's dword: the line's coefficient index, its AmbiMap scale and the gain it is formed under
-    uint32_t shared[kPasses], lineIdx[kPasses];
-    float lineScale[kPasses], lineGain[kPasses];
+    uint32_t shared[kRecordPasses], lineIdx[kRecordPasses];
+    float lineScale[kRecordPasses], lineGain[kRecordPasses];
 #pragma unroll
-    for(uint32_t pass = 0; pass < kPasses; ++pass)
+    for(uint32_t pass = 0; pass < kRecordPasses; ++pass)
     {
         const uint32_t d = lane + 64u * pass;
         uint32_t v = 0u, idx = kAmbiMax;                    // idx == kAmbiMax: not a line of this context
         float scale = 0.0f, gain = 0.0f;
-        // the filters' dwords, from the lanes that designed them (every lane takes part in the cross-lane reads)
-        const uint32_t f = (d >= kOffFilters && d < kOffHrtfDir) ? d - kOffFilters : 0u;
-        const int owner = int(f / 5u);
-        const uint32_t j = f % 5u;
-        const float c0 = __shfl(c[0], owner), c1 = __shfl(c[1], owner), c2 = __shfl(c[2], owner), c3 = __shfl(c[3], owner),
-            c4 = __shfl(c[4], owner);
-        if(d < kOffFilters)
-        {
-            switch(d)
-            {
-            case 0: v = 0u; break;
-            case 1: v = g.step; break;
-            case 2: v = uint32_t(rs.kind); break;
-            case 3: v = rs.m; break;
-            case 4: v = rs.l; break;
-            case 5: v = Bits(rs.sf); break;
-            case 6: v = rs.filterOffset; break;
-            case 7: v = flags; break;
-            default: v = uint32_t(Pick6(g.sendSlot, d - 8u)); break;
-            }
-        }
-        else if(d < kOffHrtfDir)
-            v = Bits(j == 0u ? c0 : (j == 1u ? c1 : (j == 2u ? c2 : (j == 3u ? c3 : c4))));
+        const uint32_t filter = RecordFilterDword(d, c);
+        if(d < kOffFilters) v = RecordHeadDword(d, 0u, g, rs, flags);        // (the voice: per channel, below)
+        else if(d < kOffHrtfDir) v = filter;
         else if(d < kOffDryGains) v = 0u;                   // (HRTF contexts are refused: no direction, no Hrtf.Target.Gain)
         else if(d < kOffSendGains)
         {   // ComputePanGains(&Device->Dry, coeffs, DryGain.Base, ...)
@@ -169,7 +136,7 @@ __global__ void __launch_bounds__(64) AmbiParamsKernel(SourceSetup cx, AmbiSetup
         const uint32_t row = uint32_t(rec.acn[ch]) * kAmbiMax;
         const float scale = rec.scale[ch] * coverage;
 #pragma unroll
-        for(uint32_t pass = 0; pass < kPasses; ++pass)
+        for(uint32_t pass = 0; pass < kRecordPasses; ++pass)
         {
             const uint32_t d = lane + 64u * pass;
             uint32_t v = shared[pass];
